@@ -14,6 +14,14 @@ Boards shard across ranks with no data-path collective (weak scaling); the RCCL 
 that hands observations to a single learner is timed separately and reported under
 "allgather" (serial, and overlapped with the next step on double-buffered observations).
 Rank 0 prints ONE JSON line.
+
+A plain run measures the headline figure only: set-up, clock warm-up, W warm-up steps, K timed
+steps, the JSON line.  Everything else it can measure (the out-of-cache sibling and the HBM
+asymptote, the other BASELINE configs, the Python step() API, two-stream halves, entry points,
+the cfg3 learner side, the all-gathers, the CPU baseline) runs only with --full; the --no-*
+options switch single parts of --full off.  --dump-outputs DIR writes what the last timed step
+computed (a fixed, seeded sample of the boards where the outputs exceed DUMP_BUDGET_BYTES) as
+DIR/<name>.npy; the inputs depend on the arguments alone, so two builds compare output for output.
 """
 import argparse
 import json
@@ -30,6 +38,9 @@ ACTION_SEED = 0xAC710005
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak
 COPY_CEILING_GBS = 6290.0  # measured float4 copy ceiling (/opt/skills/guides/MI355X_MICROARCH.md, chip-level table)
 INFINITY_CACHE_BYTES = 256 << 20
+SETTLE_STEPS = 1024  # fixed steps after the clock warm-up's reset (a multiple of the 16 action buffers)
+DUMP_SEED = 0x5A3B1E
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of .npy data (float32 / float64)
 
 CONFIGS = {
     # name: (size, tiles, obstacles, boards per GPU, extras)
@@ -137,6 +148,33 @@ def reference_python_recorded(cfg):
                     "(tools/time_reference_python.py); the reference cannot travel to the GPU box"}
 
 
+def dump_outputs(env, directory):
+    """--dump-outputs: what a caller of step() receives after the last timed step (observation, done, the info's flag byte and
+    step counter, reward / one-hot planes where the config has them) and the boards' cells, one DIR/<name>.npy each: float32
+    for the float32 outputs, float64 (exact) for the integer ones.  Where all boards would exceed DUMP_BUDGET_BYTES, every
+    array holds the same fixed, seeded sample of boards (ascending indices, in boards.npy)."""
+    import numpy as np
+    import torch
+    n = env.num_envs
+    outs = {"obs": env._obs, "done": env.done, "flags": env._flags, "step_count": env.step_count}
+    if env._reward is not None:
+        outs["reward"] = env._reward
+    if env._onehot is not None:
+        outs["onehot"] = env._onehot
+    per_board = sum(t.numel() // n * (4 if t.is_floating_point() else 8) for t in outs.values()) + 8 * env.n_tiles + 8
+    k = min(n, DUMP_BUDGET_BYTES // per_board)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    sel = torch.from_numpy(idx).to(env.device)
+    arrays = {name: t.index_select(0, sel) for name, t in outs.items()}
+    arrays["positions"] = env.positions.index_select(1, sel)  # [T, N] cell ids
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "boards.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        t = t.cpu()
+        np.save(os.path.join(directory, name + ".npy"), t.numpy() if t.dtype == torch.float32 else t.to(torch.float64).numpy())
+    return {"dir": directory, "boards": int(k), "of": n, "arrays": sorted(arrays) + ["boards"]}
+
+
 def spawn_ranks(n):
     """`python -m torch.distributed.run --nproc-per-node n bench.py <same arguments>` as a child
     process; returns its exit code.  Fails with a message (no hang) when the box has fewer GPUs."""
@@ -198,7 +236,15 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: take the multi-rank code path (RCCL group, max-over-ranks reduction, "
                          "all-gather timings) even with one rank; launch under torch.distributed.run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (siblings, asymptote, other configs, Python API, "
+                         "pipelined halves, entry points, learner side, all-gathers, CPU baseline); off: the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; a fixed, seeded sample "
+                         "of the boards beyond %d MiB)" % (DUMP_BUDGET_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves.  This process has not
@@ -262,7 +308,15 @@ def main():
                 env.step_async(ring[i & 15])
             torch.cuda.synchronize(device)
             clock_warmup["steps"] += 64
+        # how many steps fit the clock warm-up varies from run to run: back to the initial boards and a fixed number of steps
+        # from there (boards as far from their reset as in steady state), so that the boards of the warm-up and timed steps -
+        # and what --dump-outputs writes - depend on the arguments alone
+        env.reset()
+        for i in range(SETTLE_STEPS):
+            env.step_async(ring[i & 15])
+        torch.cuda.synchronize(device)
         clock_warmup["ms"] = (time.perf_counter() - t_w) * 1e3
+        clock_warmup["settle_steps"] = SETTLE_STEPS
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
@@ -308,10 +362,14 @@ def main():
     total_boards = n * world
     value = total_boards * args.steps / wall
 
+    # the last timed step's outputs, before anything below steps this environment again
+    if args.dump_outputs and rank == 0:
+        print("bench.py: outputs of the last timed step:", json.dumps(dump_outputs(env, args.dump_outputs)), file=sys.stderr)
+
     # the same loop through the public step() (argument staging + lazy info object, no sync):
     # what a Python learner pays per call on top of the kernel
     api = None
-    if world == 1:
+    if world == 1 and args.full:
         k = min(args.steps, 200)
         torch.cuda.synchronize(device)
         t1 = time.perf_counter()
@@ -347,7 +405,7 @@ def main():
     # HBM-bound sibling of a cache-resident headline figure
     sibling = None
     bps_cfg = algorithmic_bytes_per_board_step(cfg["size"], cfg["tiles"], cfg["onehot"], cfg["reward"])
-    if world == 1 and bps_cfg * n < INFINITY_CACHE_BYTES and not args.no_sibling:
+    if world == 1 and args.full and bps_cfg * n < INFINITY_CACHE_BYTES and not args.no_sibling:
         n_big = 4 * n
         big = VecTilerSliderEnv.random(n_big, size=cfg["size"], num_tiles=cfg["tiles"], num_obstacles=cfg["obstacles"],
                                        seed=LEVEL_SEED, multi_color=True, max_steps=2**30, device=device, auto_reset=True,
@@ -378,14 +436,14 @@ def main():
 
     # the same config at >= 3 GB per launch: the figure the Infinity Cache cannot help (roofline.hbm_asymptote)
     asymptote = None
-    if world == 1 and args.config in ASYMPTOTE_BOARDS and not args.boards and not args.no_sibling:
+    if world == 1 and args.full and args.config in ASYMPTOTE_BOARDS and not args.boards and not args.no_sibling:
         asymptote = time_asymptote(args.config, device, L, stream, args.output_memory)
 
     # cfg3's building blocks on one GPU: (a) the step into a ring of TWO observation buffers - what the overlapped hand-off of
     # float32 / uint8 observations needs (obs_buffers=2; the ring's bytes, not the launch's, decide cache residency:
     # ts_dims.ring_bytes) - and (b) the actor step that keeps NO observation (compact hand-off: the learner re-encodes)
     double_buffered = actor = None
-    if world == 1 and not args.no_sibling and not cfg["onehot"]:
+    if world == 1 and args.full and not args.no_sibling and not cfg["onehot"]:
         kw_twin = dict(multi_color=True, max_steps=2**30, device=device, auto_reset=True, with_reward=cfg["reward"])
         e2 = VecTilerSliderEnv.from_arrays(cfg["size"], env._blk, env._init, env._tgt, obs_buffers=2, output_memory=args.output_memory, **kw_twin)
         e2.reset()
@@ -413,7 +471,7 @@ def main():
     # launch policy (placement_trials = 0), with the class default (launch policy rated at construction on the first
     # allocation) and with the construction-time choice among candidate buffers (the headline's own --placement-trials).
     others = None
-    if world == 1 and args.config == "cfg1" and not args.boards and not args.no_other_configs:
+    if world == 1 and args.full and args.config == "cfg1" and not args.boards and not args.no_other_configs:
         others = {}
         for name in ("cfg2", "cfg4"):
             others[name] = time_config(name, args.placement_trials, 100, device, L, stream)
@@ -423,7 +481,7 @@ def main():
     # one half steps while it works on the other - the ramps of consecutive launches overlap.  Not the headline: the
     # synchronous step() of the reference API joins all boards every step.
     pipelined = None
-    if world == 1 and not args.no_pipelined and n % 2 == 0:
+    if world == 1 and args.full and not args.no_pipelined and n % 2 == 0:
         from tiler_slider_amd import PipelinedTilerSliderEnv
         pe = PipelinedTilerSliderEnv(n, parts=2, size=cfg["size"], num_tiles=cfg["tiles"], num_obstacles=cfg["obstacles"],
                                      seed=LEVEL_SEED, multi_color=True, max_steps=2**30, device=device, auto_reset=True,
@@ -460,18 +518,18 @@ def main():
 
     # reset() and the "scramble" (the reference's own seed -> level map on the device, ts_generate_mt19937) of this batch
     extras_us = None
-    if world == 1 and not args.no_entry_points:
+    if world == 1 and args.full and not args.no_entry_points:
         extras_us = time_entry_points(env, cfg, device, L, stream)
 
     # cfg3 (8 x 1,048,576 boards, one learner): what the learner GPU does per step after a compact / uint8 all-gather, at the
     # FULL gathered size - one ts_encode over 8,388,608 boards and one ts_expand_u8 over their 403 MB of bytes (1.6 GB out)
     learner = None
-    if world == 1 and args.config == "cfg1" and not args.boards and not args.no_learner_side:
+    if world == 1 and args.full and args.config == "cfg1" and not args.boards and not args.no_learner_side:
         learner = time_learner_side(cfg, 8 * n, device, L, stream)
         torch.cuda.empty_cache()
 
     gather = None
-    if multi and not args.no_gather:
+    if multi and args.full and not args.no_gather:
         gather = time_gathers(env, ring, world, n, dist, torch, device, min(args.steps, 20))
 
     if rank == 0:
@@ -551,7 +609,7 @@ def main():
             line["entry_points"] = extras_us
         if learner is not None:
             line["cfg3_learner_side"] = learner
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg)
         # libraries write to the process's stdout on their own (RCCL prints a version banner when the first
         # communicator is created): everything up to here went to stderr, the JSON line alone goes to stdout

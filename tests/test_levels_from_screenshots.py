@@ -4,9 +4,9 @@
 PARITY UNPINNED: the reference's parser cannot run here (cv2 absent) and tests/test_dataloader.py holds no parsed level.
 What these tests establish instead:
   * CPU: `in_range_mask` == OpenCV's documented inRange on hand-made pixels (inclusive bounds, all channels, saturation);
-    boards drawn by this file in the game's colours parse back exactly; where /root/reference/data exists (build container)
-    all 400 screenshots parse with the reference's own asserts holding and equal the committed fixture; the fixture's levels
-    satisfy the invariants the kernels rely on;
+    boards drawn by this file in the game's colours parse back exactly; the reference's screenshots kept under
+    tests/golden/screenshots (one of every (size, tiles, colour mode) group) parse with the reference's own asserts holding
+    and equal the committed fixture; the fixture's levels satisfy the invariants the kernels rely on;
   * GPU: every parsed level (grouped by shape) replayed HIP vs oracle for 64 random steps through VecTilerSliderEnv.from_levels;
   * round 5, an INDEPENDENT property of the parse (tests/level_solver.py): a breadth-first search - over the CPU oracle here, over
     batched VecTilerSliderEnv frontiers on the GPU - finds every one of the 400 levels solvable, and the least numbers of moves
@@ -20,7 +20,7 @@ import pytest
 
 from conftest import GOLDEN_DIR
 
-REF_DATA = "/root/reference/data"
+SCREENSHOTS = os.path.join(GOLDEN_DIR, "screenshots")  # the first screenshot of every (size, tiles, colour mode) group of the fixture
 
 
 def _levels_module():
@@ -173,16 +173,21 @@ def test_breadth_first_search_on_the_gpu_solves_every_parsed_level():
     _check_solutions(level_solver.solve_all(_fixture_levels(), pack_levels, level_solver.hip_expand(torch, VecTilerSliderEnv), won0))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's screenshots exist in the build container only")
-def test_all_reference_screenshots_parse_and_match_the_fixture():
+def test_reference_screenshots_parse_and_match_the_fixture():
+    """The committed screenshots (the fixture's 400 levels were parsed from all of them: make_levels_from_screenshots.py)
+    decode and parse to the fixture's levels, and between them cover every (size, tiles, colour mode) group it holds."""
     levels = _levels_module()
-    loader = levels.ImageLoader(REF_DATA)
-    assert len(loader) == 400
+    loader = levels.ImageLoader(SCREENSHOTS)
+    assert len(loader) == 9
     want = dict(_fixture_levels())
-    raw = loader[0]
-    assert raw.puzzle_image.shape == (1045, 1050, 3) and raw.level_label.shape == (80, 475, 3) and raw.target_moves.shape == (80, 400, 3)
+    groups = set()
     for i in range(len(loader)):   # the reference's asserts (dataloader.py:106-107, 118) hold inside parse_puzzle_image
-        assert loader.parse(i) == want[loader.files[i]], loader.files[i]
+        raw = loader[i]
+        assert raw.puzzle_image.shape == (1045, 1050, 3) and raw.level_label.shape == (80, 475, 3) and raw.target_moves.shape == (80, 400, 3)
+        got = loader.parse(i)
+        assert got == want[loader.files[i]], loader.files[i]
+        groups.add((got.size, len(got.initial_locations), got.multiple_colors))
+    assert groups == {(l.size, len(l.initial_locations), l.multiple_colors) for l in want.values()}
 
 
 @pytest.mark.gpu

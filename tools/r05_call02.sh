@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1 || { tail -40 $OUT/pytest_gpu.log; exit 1; }
 tail -2 $OUT/pytest_gpu.log
 timeout -k 10 200 python __graft_entry__.py smoke 2>&1 | tail -1 || exit 1
-timeout -k 10 500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_call02/bench_default.json').read().strip().splitlines()[-1])
@@ -24,7 +24,7 @@ print({k:(round(v['us'],2),round(v['frac'],3)) for k,v in d['entry_points'].item
 print(d.get('cfg3_learner_side',{}).get('encode_us'), d.get('cfg3_learner_side',{}).get('expand_us'))
 print('cpu', d['cpu_baseline']['value'], d['cpu_baseline']['cores'])
 PY
-timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --force-dist --steps 50 --warmup 10 --no-cpu-baseline --no-sibling --no-other-configs --no-entry-points --no-learner-side --no-pipelined > $OUT/bench_forced_dist_1rank_rccl.json 2> $OUT/bench_forced_dist.err || { tail -20 $OUT/bench_forced_dist.err; exit 1; }
+timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --force-dist --steps 50 --warmup 10 --no-cpu-baseline --no-sibling --no-other-configs --no-entry-points --no-learner-side --no-pipelined > $OUT/bench_forced_dist_1rank_rccl.json 2> $OUT/bench_forced_dist.err || { tail -20 $OUT/bench_forced_dist.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_call02/bench_forced_dist_1rank_rccl.json').read().strip().splitlines()[-1])
@@ -32,7 +32,7 @@ print('rccl_ranks', d.get('rccl_ranks'))
 for k,v in d['allgather'].items():
     print(k, 'serial', round(v['ms_per_step_serial'],4), 'overlapped', round(v['ms_per_step_overlapped'],4), v['bytes_per_rank_per_step'], v['actor_step'])
 PY
-timeout -k 10 300 python bench.py --config cfg4 --no-cpu-baseline --no-pipelined --no-other-configs --no-learner-side > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { tail -20 $OUT/bench_cfg4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config cfg4 --no-cpu-baseline --no-pipelined --no-other-configs --no-learner-side > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { tail -20 $OUT/bench_cfg4.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_call02/bench_cfg4.json').read().strip().splitlines()[-1])

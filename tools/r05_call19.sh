@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1 || { tail -40 $OUT/pytest_gpu.log; exit 1; }
 tail -2 $OUT/pytest_gpu.log
-timeout -k 10 300 python bench.py --config cfg4 --no-cpu-baseline --no-pipelined --no-other-configs --no-learner-side > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { tail -20 $OUT/bench_cfg4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config cfg4 --no-cpu-baseline --no-pipelined --no-other-configs --no-learner-side > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err || { tail -20 $OUT/bench_cfg4.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r05_call19/bench_cfg4.json').read().strip().splitlines()[-1])

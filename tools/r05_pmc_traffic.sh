@@ -10,7 +10,7 @@ COMMON="--no-cpu-baseline --no-pipelined --no-other-configs --no-entry-points --
 for spec in "cfg1:--config cfg1" "cfg2:--config cfg2" "cfg4:--config cfg4" "sib4m:--config cfg1 --boards 4194304"; do
   name=${spec%%:*}; args=${spec#*:}
   for c in WRITE_SIZE FETCH_SIZE; do
-    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${name}_$c -- python3 bench.py $args $COMMON > $OUT/pmc_${name}_$c.log 2>&1 || { tail -5 $OUT/pmc_${name}_$c.log; exit 1; }
+    timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${name}_$c -- python3 bench.py --full $args $COMMON > $OUT/pmc_${name}_$c.log 2>&1 || { tail -5 $OUT/pmc_${name}_$c.log; exit 1; }
   done
   echo "$name done"
 done
