@@ -2363,11 +2363,13 @@ int32_t onehot_channels(const ts_dims *d) { return d->multi_color ? 1 + d->n_til
 
 using SmallKernel = void (*)(const KArgs);
 
+// plan_launch keeps a board's cells in registers (TFIX > 0) only for T <= S * S: the forms with more tiles than cells are
+// not compiled (tests/kernel_recipes.py holds a recipe for every form that is)
 template <int TFIX, bool EXTRAS, bool NT>
 SmallKernel small_kernel_for(int S) {
   switch (S) {
-    case 1: return k_small<1, TFIX, EXTRAS, NT>;
-    case 2: return k_small<2, TFIX, EXTRAS, NT>;
+    case 1: if constexpr (TFIX <= 1) return k_small<1, TFIX, EXTRAS, NT>; else return nullptr;
+    case 2: if constexpr (TFIX <= 4) return k_small<2, TFIX, EXTRAS, NT>; else return nullptr;
     case 3: return k_small<3, TFIX, EXTRAS, NT>;
     case 4: return k_small<4, TFIX, EXTRAS, NT>;
     case 5: return k_small<5, TFIX, EXTRAS, NT>;
@@ -2401,7 +2403,7 @@ SmallKernel small_kernel(int S, int tfix) {
 template <int TFIX, bool EXTRAS>
 SmallKernel multi_kernel_for(int S) {
   switch (S) {
-    case 2: return k_multi<2, TFIX, EXTRAS, TS_MULTI_G>;
+    case 2: if constexpr (TFIX <= 4) return k_multi<2, TFIX, EXTRAS, TS_MULTI_G>; else return nullptr;  // (T <= S * S, as above)
     case 3: return k_multi<3, TFIX, EXTRAS, TS_MULTI_G>;
     case 4: return k_multi<4, TFIX, EXTRAS, TS_MULTI_G>;
     case 5: return k_multi<5, TFIX, EXTRAS, TS_MULTI_G>;
