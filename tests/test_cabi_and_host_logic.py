@@ -75,7 +75,17 @@ def test_argument_validation_precedes_any_launch():
     assert L.ts_step(None, C.byref(st), None, 0, C.byref(out), None) == _cabi.ERR_NULL
     assert L.ts_reset(C.byref(ok), None, None, None) == _cabi.ERR_NULL
     assert L.ts_reset(C.byref(ok), C.byref(st), None, None) == _cabi.ERR_NULL  # blk missing
-    assert L.ts_valid_moves(C.byref(ok), C.byref(st), None, None) == _cabi.ERR_NULL
+    # the observation entry points validate alike: NULL dims, bad dims, NULL state, NULL output (or a state without blk),
+    # and an empty batch with NULL buffers
+    dummy = (C.c_uint8 * 64)()
+    for name in ("ts_valid_moves", "ts_valid_moves4", "ts_is_won", "ts_encode", "ts_encode_u8", "ts_encode_onehot", "ts_reward"):
+        fn = getattr(L, name)
+        assert fn(C.byref(ok), C.byref(st), None, None) == _cabi.ERR_NULL, name
+        assert fn(None, C.byref(st), C.addressof(dummy), None) == _cabi.ERR_NULL, name
+        assert fn(C.byref(_cabi.Dims(8, 0, 2, 2, 0, 100, 0)), C.byref(st), C.addressof(dummy), None) == _cabi.ERR_DIMS, name
+        assert fn(C.byref(ok), None, C.addressof(dummy), None) == _cabi.ERR_NULL, name
+        assert fn(C.byref(ok), C.byref(st), C.addressof(dummy), None) == _cabi.ERR_NULL, name  # blk missing
+        assert fn(C.byref(_cabi.Dims(0, 4, 2, 2, 0, 100, 0)), None, None, None) == _cabi.OK, name
     assert L.ts_generate(C.byref(ok), C.byref(st), 1, 0, 99, None) == _cabi.ERR_DIMS  # more pieces than cells
     assert L.ts_fill_actions(-1, 0, 0, 0, None, None) == _cabi.ERR_DIMS
     assert L.ts_fill_actions(4, 0, 0, 0, None, None) == _cabi.ERR_NULL

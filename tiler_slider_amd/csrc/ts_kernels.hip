@@ -34,123 +34,10 @@
 #include "../../include/tiler_slider.h"
 #include "ts_core.h"
 
-// Tunables (defaults are the shipped configuration; tools/variant_bench.py builds A/B variants
-// by overriding them with -D).
-#ifndef TS_EMIT_UNROLL
-#define TS_EMIT_UNROLL 8
-#endif
-#ifndef TS_NT_THRESHOLD_MB  // launches that write more than this use nontemporal stores
-#define TS_NT_THRESHOLD_MB 256
-#endif
-#ifndef TS_SMALL_MIN_WAVES  // __launch_bounds__ 2nd argument (waves per SIMD) of k_small; 0 = unset
-#define TS_SMALL_MIN_WAVES 0
-#endif
-#ifndef TS_EARLY_LOADS
-#define TS_EARLY_LOADS 1
-#endif
-#ifndef TS_EMIT_WAIT_EVERY  // experiment: s_waitcnt vmcnt(0) after every N observation stores of a wave (0 = never)
-#define TS_EMIT_WAIT_EVERY 0
-#endif
-#ifndef TS_EMIT_PRIO  // s_setprio level while a wave streams its observation out (0 = unchanged)
-#define TS_EMIT_PRIO 0
-#endif
-#ifndef TS_EMIT_ALIGN  // out-of-cache emit loop: store instructions cover whole 128-byte lines (see emit_bytes_as_f32)
-#define TS_EMIT_ALIGN 1
-#endif
-#ifndef TS_ANYT_OBS_BOARDS  // experiment: boards per observation pass of k_small's any-tile-count path from 6x6 on (0 = 32, as the register path)
-#define TS_ANYT_OBS_BOARDS 0
-#endif
-#ifndef TS_EMIT_ALIGN_CACHED  // the same for the agent-scope stores of cache-resident launches
-#define TS_EMIT_ALIGN_CACHED 1
-#endif
-#ifndef TS_EMIT_SHARED  // the pieces of a line that two waves share: 0 = nontemporal like the rest, 1 = plain (write-back), 2 = agent scope
-#define TS_EMIT_SHARED 1
-#endif
-#ifndef TS_EMIT_EDGE_PLAIN  // experiment: first and last store instruction of a chunk as write-back stores
-#define TS_EMIT_EDGE_PLAIN 0
-#endif
-#ifndef TS_ABLATE_DENSE  // store-only ablation: 0 = near-zeros, 1 = observation-like data (1 byte in 8 non-zero), 2 = every float non-zero
-#define TS_ABLATE_DENSE 0
-#endif
-#ifndef TS_ABLATE_LOADS
-#define TS_ABLATE_LOADS 0
-#endif
-#ifndef TS_ABLATE  // development only (tools/variant_bench.py): 1 = skip the observation stores, 2 = k_small: only those
-#define TS_ABLATE 0
-#endif
-#ifndef TS_PLANES_FIRST  // k_small launches with observation AND one-hot planes: -1 = by shape (k_small), 0 / 1 = observation / planes first
-#define TS_PLANES_FIRST -1
-#endif
-#ifndef TS_MAX_TFIX  // largest tile count with a register-resident instantiation of k_small (4, 6 or 8)
-#define TS_MAX_TFIX 8
-#endif
-#ifndef TS_XCD_REMAP
-#define TS_XCD_REMAP 1
-#endif
-#ifndef TS_XCD_PIECE_POLICY  // out-of-cache launches with short chunks per wave: pieces of P blocks per XCD (piece_policy)
-#define TS_XCD_PIECE_POLICY 64
-#endif
-#ifndef TS_XCD_PIECE_LONG  // the same for chunks of 8 KB and more of the one-lane-per-board kernels
-#define TS_XCD_PIECE_LONG 32
-#endif
-#ifndef TS_XCD_PIECE_LINES  // and for the kernels that deal a board over several lanes (k_lines, k_deal)
-#define TS_XCD_PIECE_LINES 16
-#endif
-#ifndef TS_XCD_PIECE  // experiment (all launches, compile time): 0 = as the policy; P > 0 = pieces of P blocks, round-robin
-#define TS_XCD_PIECE 0
-#endif
-#ifndef TS_MULTI_G  // boards per lane of k_multi (2 or 4); 0 = never launch it
-#define TS_MULTI_G 2
-#endif
-#ifndef TS_MULTI_MIN_BOARDS  // below this many boards k_small's four times as many waves fill the chip better
-#define TS_MULTI_MIN_BOARDS 1048576
-#endif
-#ifndef TS_WAVES_PER_BLOCK
-#define TS_WAVES_PER_BLOCK 4
-#endif
-#ifndef TS_DEAL_LANES4_MAX  // k_deal: up to this many tiles a board is dealt over 4 lanes, above over 8
-#define TS_DEAL_LANES4_MAX 32
-#endif
-#ifndef TS_LINES_LDS_PAD  // diagnostic: extra dynamic LDS per wave of k_lines (lowers the resident waves)
-#define TS_LINES_LDS_PAD 0
-#endif
-#ifndef TS_LINES_WAVES  // waves per block of k_lines
-#define TS_LINES_WAVES 4
-#endif
-#ifndef TS_LINES_OOC_BPW  // experiment: boards per wave of k_lines for out-of-cache launches (0 = 4)
-#define TS_LINES_OOC_BPW 0
-#endif
-#ifndef TS_SMALL_OOC_BPW  // boards per wave of k_small for out-of-cache launches: 0 = the measured policy, else forced
-#define TS_SMALL_OOC_BPW 0
-#endif
-#ifndef TS_SMALL_LDS_PAD  // diagnostic: extra dynamic LDS per wave of k_small
-#define TS_SMALL_LDS_PAD 0
-#endif
-// Launches whose output cannot stay in the Infinity Cache (the ones that use nontemporal stores):
-// waves per block and blocks per CU.  -1 = the measured policy (ooc_residency below), 0 = no bound
-// (as many as registers / LDS admit: round 1's behaviour), > 0 = forced (tools/variant_bench.py sweeps).
-#ifndef TS_OOC_WAVES
-#define TS_OOC_WAVES -1
-#endif
-#ifndef TS_OOC_BLOCKS
-#define TS_OOC_BLOCKS -1
-#endif
-#ifndef TS_FORCE_OBS_BOARDS  // diagnostic: 64 = round 1's one-pass observation image at every size
-#define TS_FORCE_OBS_BOARDS 0
-#endif
-#ifndef TS_MAX_BLOCK_LDS  // dynamic LDS a block may ask for (bytes)
-#define TS_MAX_BLOCK_LDS (64 * 1024)
-#endif
-#ifndef TS_EXP_MC_FLAG_WORD  // experiment (round 5, cfg4): the record word multi-colour launches of k_lines read the duplicate-target flag
-#define TS_EXP_MC_FLAG_WORD 16  // from.  16 = the shipped layout (second 64-byte half of the record); 0 = a word of the first half, so that
-#endif                          // a launch touches 64 of the record's 128 bytes (timing only: right answers only on levels without duplicates, S <= 15)
-#ifndef TS_SET_LDS_ATTR  // diagnostic: hipFuncSetAttribute(MaxDynamicSharedMemorySize) before k_small launches
-#define TS_SET_LDS_ATTR 0
-#endif
-
 namespace {
 
 constexpr int kWave = 64;
+constexpr int kWavesPerBlock = 4;  // waves per block of k_small, k_multi and k_deal where no residency bound sets fewer
 
 enum Op : uint32_t { OP_STEP = 0, OP_RESET = 1, OP_OBSERVE = 2 };
 
@@ -227,14 +114,10 @@ __device__ __forceinline__ f32x4 bytes_to_f4(uint32_t w) {
 __device__ __forceinline__ void store16_agent_scope(void *dst, f32x4 v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v));
 }
-// 1 = plain (write-back in the XCD's L2), 2 = agent scope; as instructions, so that no optimisation pass can fold them into a
-// neighbouring nontemporal store (with the same wait states behind them as above)
-template <int POLICY>
-__device__ __forceinline__ void store16_policy(void *dst, f32x4 v) {
-  if constexpr (POLICY == 2)
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v));
-  else
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(dst), "v"(v));
+// A plain (write-back in the XCD's L2) store, as an instruction, so that no optimisation pass can fold it into a neighbouring
+// nontemporal store (with the same wait states behind it as above)
+__device__ __forceinline__ void store16_writeback(void *dst, f32x4 v) {
+  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(dst), "v"(v));
 }
 __device__ __forceinline__ void store4_agent_scope(void *dst, uint32_t v) {
   asm volatile("global_store_dword %0, %1, off sc1" ::"v"(dst), "v"(v));
@@ -255,84 +138,61 @@ __device__ __forceinline__ void store_f4(f32x4 *dst, f32x4 v) {
 // `dst` is 16-B aligned; img is 16-B aligned.  NT (nontemporal stores) is a template parameter in
 // k_small / k_lines: the cache-resident and the out-of-cache launch are different instantiations,
 // so a profile lists them as different kernels.
-template <bool NT, bool ANY_START = false, int UNROLL = TS_EMIT_UNROLL>
+constexpr int kEmitUnroll = 8;  // store instructions per unrolled step of the nontemporal emit loop
+
+template <bool NT, bool ANY_START = false, int UNROLL = kEmitUnroll>
 __device__ __forceinline__ void emit_bytes_as_f32(const unsigned char *img, float *dst, int nfl, int lane, uint32_t edges = 0) {
   const int nf4 = nfl >> 2;
   const uint32_t *w = reinterpret_cast<const uint32_t *>(img);
   f32x4 *d4 = reinterpret_cast<f32x4 *>(dst);
-#if TS_EMIT_PRIO > 0
-  __builtin_amdgcn_s_setprio(TS_EMIT_PRIO);
-#endif
-#if TS_ABLATE == 1
-  if (nfl == -12345)  // never true: keeps the code, drops the traffic
-#endif
-  {
-#if TS_EMIT_WAIT_EVERY > 0
-    // experiment: at most TS_EMIT_WAIT_EVERY KiB of this wave's observation stores in flight
-    int issued = 0;
-    for (int q = lane; q < nf4; q += kWave) {
-      store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
-      if (++issued == TS_EMIT_WAIT_EVERY) {
-        issued = 0;
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only (gfx9 encoding: expcnt 7, lgkmcnt 15)
+  if constexpr (NT) {
+    // Store instructions that cover whole 128-byte lines (round 3, tools/align_probe.*, profiles/r03_align_probe.log).
+    // A wave's chunk starts wherever its first board starts: at 12 * S * S * n0 bytes, a multiple of 128 only for
+    // even board sizes (k_small's 32 / 64 boards per wave always are).  With `dst` m sixteenths of a line past a line
+    // start, lane l of instruction k used to store unit 64 k + l of the chunk: every instruction then began and ended
+    // inside a line, and nontemporal stores of partial lines cost a quarter of the write rate (15x15: 5.3 -> 6.9 TB/s
+    // in the store-only probe) even though the next instruction of the same wave completes the line.  Here instruction k
+    // stores units 64 k + l - m: whole lines, except the first and last line of the chunk, which the neighbouring
+    // waves share; those pieces go out as plain (write-back) stores, so that the two halves meet in the XCD's L2.
+    // (k_small's chunks start on a line except for quarter waves of odd board sizes - 7x7: 9,408 B; computing m costs two instructions)
+    const int m = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7u);
+    const int total = nf4 + m, iters = (total + kWave - 1) >> 6;
+    const int last_line = total >> 3;
+    const bool tail_shared = (total & 7) != 0;
+    auto edge = [&](int k, bool whole) {  // first / last instruction of the chunk: predicated, shared pieces write-back
+      const int u = k * kWave + lane, q = u - m;
+      if (q >= 0 && q < nf4) {
+        const f32x4 v = bytes_to_f4(w[q]);
+        const bool shared = (m != 0 && u < 8) || (tail_shared && (u >> 3) == last_line);
+        // (an asm statement: written as two C++ stores the compiler merges the branches into ONE store and drops the
+        // nontemporal hint of the whole instruction - a third of a 4x4 half wave's stores went out plain, 134 -> 227 us)
+        if (shared || whole)
+          store16_writeback(&d4[q], v);
+        else
+          __builtin_nontemporal_store(v, &d4[q]);
       }
-    }
-#else
-    if constexpr (NT) {
-#if TS_EMIT_ALIGN
-      // Store instructions that cover whole 128-byte lines (round 3, tools/align_probe.*, profiles/r03_align_probe.log).
-      // A wave's chunk starts wherever its first board starts: at 12 * S * S * n0 bytes, a multiple of 128 only for
-      // even board sizes (k_small's 32 / 64 boards per wave always are).  With `dst` m sixteenths of a line past a line
-      // start, lane l of instruction k used to store unit 64 k + l of the chunk: every instruction then began and ended
-      // inside a line, and nontemporal stores of partial lines cost a quarter of the write rate (15x15: 5.3 -> 6.9 TB/s
-      // in the store-only probe) even though the next instruction of the same wave completes the line.  Here instruction k
-      // stores units 64 k + l - m: whole lines, except the first and last line of the chunk, which the neighbouring
-      // waves share; those pieces go out as plain (write-back) stores, so that the two halves meet in the XCD's L2.
-      // (k_small's chunks start on a line except for quarter waves of odd board sizes - 7x7: 9,408 B; computing m costs two instructions)
-      const int m = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7u);
-      const int total = nf4 + m, iters = (total + kWave - 1) >> 6;
-      const int last_line = total >> 3;
-      const bool tail_shared = (total & 7) != 0;
-      auto edge = [&](int k, bool whole) {  // first / last instruction of the chunk: predicated, shared pieces write-back
-        const int u = k * kWave + lane, q = u - m;
-        if (q >= 0 && q < nf4) {
-          const f32x4 v = bytes_to_f4(w[q]);
-          const bool shared = (m != 0 && u < 8) || (tail_shared && (u >> 3) == last_line);
-          // (an asm statement: written as two C++ stores the compiler merges the branches into ONE store and drops the
-          // nontemporal hint of the whole instruction - a third of a 4x4 half wave's stores went out plain, 134 -> 227 us)
-          if ((shared && TS_EMIT_SHARED != 0) || whole)
-            store16_policy<TS_EMIT_SHARED == 2 ? 2 : 1>(&d4[q], v);
-          else
-            __builtin_nontemporal_store(v, &d4[q]);
-        }
-      };
-      // `edges` (KArgs.emit_edges, chosen per launch on the host): bit 0 / bit 1 = the chunk's first / last store instruction
-      // goes out as a write-back store as a whole (see edge_policy)
-      edge(0, (edges & 1u) != 0 || TS_EMIT_EDGE_PLAIN);
-      const uint32_t *wm = w - m;
-      f32x4 *dm = d4 - m;
+    };
+    // `edges` (KArgs.emit_edges, chosen per launch on the host): bit 0 / bit 1 = the chunk's first / last store instruction
+    // goes out as a write-back store as a whole (see edge_policy)
+    edge(0, (edges & 1u) != 0);
+    const uint32_t *wm = w - m;
+    f32x4 *dm = d4 - m;
 #pragma unroll UNROLL
-      for (int u = kWave + lane; u < (iters - 1) * kWave; u += kWave) __builtin_nontemporal_store(bytes_to_f4(wm[u]), &dm[u]);
-      if (iters > 1) edge(iters - 1, (edges & 2u) != 0 || TS_EMIT_EDGE_PLAIN);
-#else
-#pragma unroll TS_EMIT_UNROLL
-      for (int q = lane; q < nf4; q += kWave) store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
-#endif
+    for (int u = kWave + lane; u < (iters - 1) * kWave; u += kWave) __builtin_nontemporal_store(bytes_to_f4(wm[u]), &dm[u]);
+    if (iters > 1) edge(iters - 1, (edges & 2u) != 0);
+  } else {
+    // the agent-scope store is an asm statement - a convergent operation to the compiler, which does not unroll a
+    // loop around one with a run-time remainder; a hand-unrolled version measured the same (30.2 vs 30.2 us at cfg1)
+    if constexpr (ANY_START) {
+      // whole-line store instructions for cache-resident launches of k_lines too, whose chunks start anywhere for odd
+      // board sizes (15x15 at 65,536 boards 29.2 -> 28.5 us, 11x11 29.1 -> 28.3); k_small / k_multi chunks always start
+      // on a line, and the extra lane test costs them 1 % (cfg1 30.07 -> 30.36), hence the template flag
+      const int m = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7u);
+      for (int q = lane - m; q < nf4; q += kWave)
+        if (q >= 0) store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
     } else {
-      // the agent-scope store is an asm statement - a convergent operation to the compiler, which does not unroll a
-      // loop around one with a run-time remainder; a hand-unrolled version measured the same (30.2 vs 30.2 us at cfg1)
-      if constexpr (ANY_START && TS_EMIT_ALIGN_CACHED) {
-        // whole-line store instructions for cache-resident launches of k_lines too, whose chunks start anywhere for odd
-        // board sizes (15x15 at 65,536 boards 29.2 -> 28.5 us, 11x11 29.1 -> 28.3); k_small / k_multi chunks always start
-        // on a line, and the extra lane test costs them 1 % (cfg1 30.07 -> 30.36), hence the template flag
-        const int m = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7u);
-        for (int q = lane - m; q < nf4; q += kWave)
-          if (q >= 0) store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
-      } else {
-        for (int q = lane; q < nf4; q += kWave) store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
-      }
+      for (int q = lane; q < nf4; q += kWave) store_f4<NT>(&d4[q], bytes_to_f4(w[q]));
     }
-#endif
   }
   const int tail = nfl & 3;  // only on the last, partial tile of odd-sized boards
   if (lane < tail) dst[nf4 * 4 + lane] = (float)img[nf4 * 4 + lane];
@@ -349,9 +209,6 @@ __device__ __forceinline__ void emit_bytes_raw(const unsigned char *img, uint8_t
   const int nv = nbytes / VEC;
   const vec_t *src = reinterpret_cast<const vec_t *>(img);
   vec_t *d = reinterpret_cast<vec_t *>(dst);
-#if TS_ABLATE == 1
-  if (nbytes == -12345)
-#endif
   for (int q = lane; q < nv; q += kWave) {
     if constexpr (NT) {
       if constexpr (VEC == 16)
@@ -381,12 +238,7 @@ __device__ __forceinline__ M load_blk(const uint32_t *blk, int64_t N, int64_t n)
 // k_small: S <= 8, one board per lane.  TFIX in 1..8: n_tiles == n_targets == TFIX, positions
 // live in registers; TFIX == 0: any tile count, positions staged in LDS.
 // ------------------------------------------------------------------------------------------
-#define TS_SMALL_THREADS (TS_WAVES_PER_BLOCK * 64 > 256 ? TS_WAVES_PER_BLOCK * 64 : 256)
-#if TS_SMALL_MIN_WAVES > 0
-#define TS_SMALL_BOUNDS __launch_bounds__(TS_SMALL_THREADS, TS_SMALL_MIN_WAVES)
-#else
-#define TS_SMALL_BOUNDS __launch_bounds__(TS_SMALL_THREADS)
-#endif
+constexpr int kSmallThreads = kWavesPerBlock * kWave > 256 ? kWavesPerBlock * kWave : 256;  // __launch_bounds__ of k_small
 
 // Blocks are dealt round-robin over the 8 XCDs (observed, not contractual: speed only; tools/archive/xcc_probe.py read
 // HW_REG_XCC_ID == blockIdx % 8 for every block of every launch shape used here, profiles/r02_xcc_probe.log).  This
@@ -404,10 +256,6 @@ __device__ __forceinline__ M load_blk(const uint32_t *blk, int64_t N, int64_t n)
 // x * s blocks into its eighth / piece, s = 1 .. 11 (x 97 for eighths) - and the order of the blocks inside a piece (ascending,
 // bit-reversed, descending) change NOTHING, every cell of the grid within 0.5 %; the piece size does: profiles/r04_contig_sweep.log.)
 __device__ __forceinline__ uint32_t xcd_contiguous_block(uint32_t bid, uint32_t nblocks, uint32_t piece = 0) {
-#if TS_XCD_REMAP
-#if TS_XCD_PIECE > 0
-  piece = TS_XCD_PIECE;
-#endif
   if (piece > 0 && piece < (1u << 24)) {
     const uint32_t full = nblocks / (8u * piece) * (8u * piece);
     if (bid >= full) return bid;
@@ -416,31 +264,24 @@ __device__ __forceinline__ uint32_t xcd_contiguous_block(uint32_t bid, uint32_t 
   }
   const uint32_t q = nblocks >> 3, r = nblocks & 7u, xcd = bid & 7u;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-#else
-  return bid;
-#endif
 }
 
 // boards per observation pass of k_small (also used by the host to size the LDS carve)
 // (Round 3 tried a smaller image for the any-tile-count path, whose long serial slide loop is latency-bound - 16 boards per
 // pass: 8x8 with 20 tiles 16 KB -> 5.5 KB of LDS per wave, 8 -> 28 waves per CU - for 97.2 -> 94.8 us there, 91.8 -> 86.5 with 12
-// tiles, but 82.0 -> 85.4 at 6x6 / 12 tiles and 38.7 -> 39.7 cache-resident: not shipped, TS_ANYT_OBS_BOARDS.)
-constexpr int small_obs_boards(int C, bool any_t = false) {
-  // (a pass must start on a 128-byte line of the output: 12 * C * boards % 128 == 0 - true for 6x6 and 8x8 with 16 boards)
-  return TS_FORCE_OBS_BOARDS ? TS_FORCE_OBS_BOARDS
-         : (kWave * 3 * C <= 6144 ? kWave : (any_t && TS_ANYT_OBS_BOARDS && (12 * C * TS_ANYT_OBS_BOARDS) % 128 == 0) ? TS_ANYT_OBS_BOARDS : kWave / 2);
-}
+// tiles, but 82.0 -> 85.4 at 6x6 / 12 tiles and 38.7 -> 39.7 cache-resident: not shipped.)
+constexpr int small_obs_boards(int C) { return kWave * 3 * C <= 6144 ? kWave : kWave / 2; }
 
 constexpr int kSmallBatch = 8;  // global loads in flight per lane in the any-T tile / target loops
 
 // EXTRAS = false compiles the optional outputs (legality mask, reward, one-hot) out, so the
 // plain step / reset / encode path does not carry their registers and code.
 template <int S, int TFIX, bool EXTRAS, bool NT>
-__global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
+__global__ __launch_bounds__(kSmallThreads) void k_small(const KArgs a) {
   using BB = ts::Bitboard<S>;
   using M = typename BB::mask_t;
   constexpr int C = BB::C;
-  constexpr int kObsBoards = small_obs_boards(C, TFIX == 0);
+  constexpr int kObsBoards = small_obs_boards(C);
   constexpr int kImg = kObsBoards * 3 * C;  // bytes, multiple of 16 (kObsBoards is 32 or 64)
   constexpr int TR = TFIX > 0 ? TFIX : 1;
 
@@ -461,28 +302,6 @@ __global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
   const bool mc = a.mc != 0;
 
   unsigned char *img = smem + (size_t)wave * a.lds_wave_bytes;
-#if TS_ABLATE == 2  // development only: the observation stores alone (no state loads, no transition)
-  if (a.obs) {
-    for (int c0 = 0; c0 < nb; c0 += kObsBoards) {
-      if (c0) wave_sync();
-      for (int off = lane * 16; off < kImg; off += kWave * 16) *reinterpret_cast<uint4 *>(img + off) = TS_ABLATE_DENSE == 2 ? make_uint4(0x04030201u + lane, 0x08070605u, 0x0c0b0a09u + off, 0x100f0e0du)
-                                                                                                            : TS_ABLATE_DENSE ? make_uint4(1, 0, 0x0200, 0) : make_uint4(0, 0, lane & 1, 0);
-#if TS_ABLATE_LOADS
-      {  // + the state loads of a plain step, consumed by one LDS byte
-        const int64_t nl = (n0 + lane) < a.N ? n0 + lane : a.N - 1;
-        uint32_t x = a.blk[nl] ^ a.done[nl] ^ (uint32_t)a.step_count[nl] ^ a.actions[nl];
-        for (int t = 0; t < TR; ++t) x ^= a.pos[(int64_t)t * a.N + nl] ^ a.tgt[(int64_t)t * a.N + nl];
-        wave_sync();
-        img[lane * 3 * C] = (unsigned char)(x & 1);
-      }
-#endif
-      wave_sync();
-      const int nbb = (nb - c0) < kObsBoards ? (nb - c0) : kObsBoards;
-      emit_bytes_as_f32<NT>(img, a.obs + (n0 + c0) * (3 * C), nbb * 3 * C, lane, a.emit_edges);
-    }
-    return;
-  }
-#endif
   unsigned char *stage = img + a.lds_stage_off;
   unsigned char *st_np = stage;                                 // [T][64] post-move cells
   unsigned char *st_tg = st_np + (size_t)T * kWave;             // [Tt][64] target cells
@@ -587,7 +406,7 @@ __global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
       ordered &= q[t] == tg[t];
       occ2 |= M(1) << q[t];
       tgm |= M(1) << tg[t];
-      if (live && kind != 1 && TS_ABLATE != 3) a.pos[(int64_t)t * N + n] = (uint8_t)q[t];
+      if (live && kind != 1) a.pos[(int64_t)t * N + n] = (uint8_t)q[t];
     }
   } else {
     for (int t = 0; t < T; ++t) {
@@ -640,15 +459,15 @@ __global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
       d = 1u;
       flags |= TS_FLAG_TIMEOUT;
     }
-    if (live && TS_ABLATE != 3) {
+    if (live) {
       a.step_count[n] = sc;
       a.done[n] = (uint8_t)d;
     }
-  } else if (kind == 2 && live && TS_ABLATE != 3) {
+  } else if (kind == 2 && live) {
     a.step_count[n] = 0;
     a.done[n] = 0;
   }
-  if (live && a.flags && (TS_ABLATE != 3 || flags == 0xEE)) a.flags[n] = (uint8_t)flags;
+  if (live && a.flags) a.flags[n] = (uint8_t)flags;
 
   // ---- legality mask of the post-move board (environment.py:149-171) ----
   if (EXTRAS && (a.valid || a.valid4)) {
@@ -743,7 +562,7 @@ __global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
   // observation first.  (Also tried there: a vmcnt(0) wait between the two streams - slower on fast buffers; write-back stores
   // for either stream - 119 -> 147 us.  The narrow state stores - cells, counters, flags - belong BEFORE the big streams: behind
   // them cfg2 109.0 -> 112.3 us, cfg4 108.3 -> 117.6, 8x8 with four tiles 71.3 -> 77.1: profiles/r04_state_stores_last.log.)
-  constexpr bool kPlanesFirstShape = TS_PLANES_FIRST < 0 ? (NT && S == 5) : TS_PLANES_FIRST != 0;
+  constexpr bool kPlanesFirstShape = NT && S == 5;
   const bool planes_first = EXTRAS && kPlanesFirstShape && a.onehot && a.oh_boards > 0;
   if ((a.obs || a.obs_u8) && !planes_first) emit_observation();
 
@@ -848,11 +667,8 @@ __global__ TS_SMALL_BOUNDS void k_small(const KArgs a) {
 // ------------------------------------------------------------------------------------------
 template <int G> struct MultiPack;
 template <> struct MultiPack<2> { using bytes_t = uint16_t; using words_t = uint2; };
-template <> struct MultiPack<4> { using bytes_t = uint32_t; using words_t = uint4; };
 __device__ __forceinline__ uint32_t word_of(const uint2 &v, int g) { return g == 0 ? v.x : v.y; }
-[[maybe_unused]] __device__ __forceinline__ uint32_t word_of(const uint4 &v, int g) { return g == 0 ? v.x : g == 1 ? v.y : g == 2 ? v.z : v.w; }
 __device__ __forceinline__ void set_word(uint2 &v, int g, uint32_t x) { (g == 0 ? v.x : v.y) = x; }
-[[maybe_unused]] __device__ __forceinline__ void set_word(uint4 &v, int g, uint32_t x) { (g == 0 ? v.x : g == 1 ? v.y : g == 2 ? v.z : v.w) = x; }
 
 template <int S, int TFIX, bool EXTRAS, int G>
 __global__ __launch_bounds__(256) void k_multi(const KArgs a) {
@@ -1354,6 +1170,7 @@ __global__ __launch_bounds__(256, (S == 8 && TPL <= 7 && !EXTRAS ? 8 : 1)) void 
 // ------------------------------------------------------------------------------------------
 constexpr int kLinesG = 16;                   // lanes per board of ts_prepare's mapping (and the default of k_lines)
 constexpr int kLinesBPW = kWave / kLinesG;    // boards per wave with 16 lanes per board
+constexpr int kLinesWaves = 4;               // waves per block of k_lines (fewer beyond the Infinity Cache: lines_waves_policy)
 constexpr int lines_record_words(bool wide) { return wide ? 128 : 32; }
 // Record of one board in ts_state.lines (uint32 words; include/tiler_slider.h):
 //   S <= 16: w[j] = Br[j] | Bc[j] << 16 (j < 16)     w[16 + j] = Tm[j]     bit 31 of w[16]: duplicate targets
@@ -1367,7 +1184,7 @@ constexpr int lines_record_words(bool wide) { return wide ? 128 : 32; }
 // table loads, LDS set-up, three wave syncs).
 
 template <bool WIDE, int LPB, int TPL, bool NT, bool EXTRAS>
-__global__ __launch_bounds__(TS_LINES_WAVES * 64) void k_lines(const KArgs a, const int S, const uint32_t invS) {
+__global__ __launch_bounds__(kLinesWaves * kWave) void k_lines(const KArgs a, const int S, const uint32_t invS) {
   using cell_t = typename std::conditional<WIDE, uint16_t, uint8_t>::type;
   constexpr int G = LPB, BPW = kWave / LPB;
   constexpr int NLN = WIDE ? 32 : 16;  // line slots of one board
@@ -1416,7 +1233,7 @@ __global__ __launch_bounds__(TS_LINES_WAVES * 64) void k_lines(const KArgs a, co
       wx[i] = rec[mc ? 96 : 64 + line];
     } else {
       wC[i] = 0;
-      wx[i] = rec[mc ? TS_EXP_MC_FLAG_WORD : 16 + line];
+      wx[i] = rec[mc ? 16 : 16 + line];
     }
   }
   const cell_t *g_pos = reinterpret_cast<const cell_t *>(a.pos);
@@ -2334,7 +2151,9 @@ __global__ __launch_bounds__(256) void k_fill_actions(uint8_t *actions, int64_t 
 // Host side of the C-ABI
 // ------------------------------------------------------------------------------------------
 thread_local int32_t t_last_hip_error = 0;
-std::atomic<int64_t> g_multi_min_boards{TS_MULTI_MIN_BOARDS};  // ts_tuning(TS_TUNE_MULTI_MIN_BOARDS)
+constexpr int64_t kMultiMinBoards = 1048576;        // below this many boards k_small's four times as many waves fill the chip better
+constexpr int64_t kNtThresholdBytes = 256ll << 20;  // launches that write more than this use nontemporal stores
+std::atomic<int64_t> g_multi_min_boards{kMultiMinBoards};  // ts_tuning(TS_TUNE_MULTI_MIN_BOARDS)
 std::atomic<int64_t> g_lines_lanes{0};  // ts_tuning(TS_TUNE_LINES_LANES): 0 = by tile count, 4 / 8 / 16 = forced where instantiated
 std::atomic<int64_t> g_lines_bpw{0};    // ts_tuning(TS_TUNE_LINES_BPW): 0 = policy, else boards per wave of k_lines (the other lanes idle)
 std::atomic<int64_t> g_xcd_piece{INT64_MAX};  // ts_tuning(TS_TUNE_XCD_PIECE): INT64_MAX = policy, 0 = eighths, P = pieces of P blocks (out-of-cache launches)
@@ -2346,7 +2165,7 @@ std::atomic<int64_t> g_lines_waves{0};  // ts_tuning(TS_TUNE_LINES_WAVES): 0 = p
 std::atomic<int64_t> g_state_only{1};    // ts_tuning(TS_TUNE_STATE_ONLY): 0 = launches without an image output stay on k_lines above 8x8
 std::atomic<int64_t> g_deal_enabled{1};  // ts_tuning(TS_TUNE_DEAL): 0 = boards up to 8x8 with more than 8 tiles stay on k_small's one-lane path
 std::atomic<int64_t> g_emit_edges{4};   // ts_tuning(TS_TUNE_EMIT_EDGES): 0 .. 3 forced, 4 = policy
-std::atomic<int64_t> g_nt_threshold_bytes{(int64_t)TS_NT_THRESHOLD_MB * 1024 * 1024};  // ts_tuning(TS_TUNE_NT_THRESHOLD_BYTES)
+std::atomic<int64_t> g_nt_threshold_bytes{kNtThresholdBytes};  // ts_tuning(TS_TUNE_NT_THRESHOLD_BYTES)
 
 int32_t check_dims(const ts_dims *d) {
   if (!d) return TS_ERR_NULL;
@@ -2362,107 +2181,98 @@ int32_t check_dims(const ts_dims *d) {
 int32_t onehot_channels(const ts_dims *d) { return d->multi_color ? 1 + d->n_tiles + d->n_targets : 3; }
 
 using SmallKernel = void (*)(const KArgs);
+using LinesKernel = void (*)(const KArgs, const int, const uint32_t);
 
-// plan_launch keeps a board's cells in registers (TFIX > 0) only for T <= S * S: the forms with more tiles than cells are
-// not compiled (tests/kernel_recipes.py holds a recipe for every form that is)
-template <int TFIX, bool EXTRAS, bool NT>
-SmallKernel small_kernel_for(int S) {
-  switch (S) {
-    case 1: if constexpr (TFIX <= 1) return k_small<1, TFIX, EXTRAS, NT>; else return nullptr;
-    case 2: if constexpr (TFIX <= 4) return k_small<2, TFIX, EXTRAS, NT>; else return nullptr;
-    case 3: return k_small<3, TFIX, EXTRAS, NT>;
-    case 4: return k_small<4, TFIX, EXTRAS, NT>;
-    case 5: return k_small<5, TFIX, EXTRAS, NT>;
-    case 6: return k_small<6, TFIX, EXTRAS, NT>;
-    case 7: return k_small<7, TFIX, EXTRAS, NT>;
-    case 8: return k_small<8, TFIX, EXTRAS, NT>;
-    default: return nullptr;
-  }
+// Kernel selection, the same in every family: by_value<K, V...>(v, f) is f(std::integral_constant<int, V>{}) for the V equal
+// to v (nullptr for any other v), by_flag<K>(b, f) is f(std::bool_constant<b>{}); f names the instantiation, or nullptr for a
+// form that is not compiled.  tests/kernel_recipes.py holds a recipe for every form that is.
+template <class K, int... Vs, class F>
+K by_value(int v, F f) {
+  K k = nullptr;
+  (void)((v == Vs && (k = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return k;
+}
+template <class K, class F>
+K by_flag(bool b, F f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
-template <bool EXTRAS, bool NT>
-SmallKernel small_kernel(int S, int tfix) {
-  switch (tfix) {
-    case 1: return small_kernel_for<1, EXTRAS, NT>(S);
-    case 2: return small_kernel_for<2, EXTRAS, NT>(S);
-    case 3: return small_kernel_for<3, EXTRAS, NT>(S);
-    case 4: return small_kernel_for<4, EXTRAS, NT>(S);
-#if TS_MAX_TFIX >= 6
-    case 5: return small_kernel_for<5, EXTRAS, NT>(S);
-    case 6: return small_kernel_for<6, EXTRAS, NT>(S);
-#endif
-#if TS_MAX_TFIX >= 8
-    case 7: return small_kernel_for<7, EXTRAS, NT>(S);
-    case 8: return small_kernel_for<8, EXTRAS, NT>(S);
-#endif
-    default: return small_kernel_for<0, EXTRAS, NT>(S);
-  }
+// k_small: S <= 8; TFIX = 0 (any tile count) or 1 .. 8 tiles in registers, the latter only for T <= S * S
+SmallKernel small_kernel(int S, int tfix, bool extras, bool nt) {
+  return by_flag<SmallKernel>(extras, [&](auto e) {
+    return by_flag<SmallKernel>(nt, [&](auto n) {
+      return by_value<SmallKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [&](auto s) {
+        return by_value<SmallKernel, 0, 1, 2, 3, 4, 5, 6, 7, 8>(tfix, [&](auto t) -> SmallKernel {
+          if constexpr (t <= s * s) return k_small<s, t, e, n>; else return nullptr;
+        });
+      });
+    });
+  });
 }
 
-#if TS_MULTI_G > 0
-template <int TFIX, bool EXTRAS>
-SmallKernel multi_kernel_for(int S) {
-  switch (S) {
-    case 2: if constexpr (TFIX <= 4) return k_multi<2, TFIX, EXTRAS, TS_MULTI_G>; else return nullptr;  // (T <= S * S, as above)
-    case 3: return k_multi<3, TFIX, EXTRAS, TS_MULTI_G>;
-    case 4: return k_multi<4, TFIX, EXTRAS, TS_MULTI_G>;
-    case 5: return k_multi<5, TFIX, EXTRAS, TS_MULTI_G>;
-    default: return nullptr;
-  }
+constexpr int kMultiBoardsPerLane = 2;  // k_multi's G
+
+// k_multi: 2x2 .. 5x5 with 1 .. 8 tiles in registers (T <= S * S), kMultiBoardsPerLane boards per lane
+SmallKernel multi_kernel(int S, int tfix, bool extras) {
+  return by_flag<SmallKernel>(extras, [&](auto e) {
+    return by_value<SmallKernel, 2, 3, 4, 5>(S, [&](auto s) {
+      return by_value<SmallKernel, 1, 2, 3, 4, 5, 6, 7, 8>(tfix, [&](auto t) -> SmallKernel {
+        if constexpr (t <= s * s) return k_multi<s, t, e, kMultiBoardsPerLane>; else return nullptr;
+      });
+    });
+  });
 }
 
-template <bool EXTRAS>
-SmallKernel multi_kernel(int S, int tfix) {
-  switch (tfix) {
-    case 1: return multi_kernel_for<1, EXTRAS>(S);
-    case 2: return multi_kernel_for<2, EXTRAS>(S);
-    case 3: return multi_kernel_for<3, EXTRAS>(S);
-    case 4: return multi_kernel_for<4, EXTRAS>(S);
-#if TS_MAX_TFIX >= 6
-    case 5: return multi_kernel_for<5, EXTRAS>(S);
-    case 6: return multi_kernel_for<6, EXTRAS>(S);
-#endif
-#if TS_MAX_TFIX >= 8
-    case 7: return multi_kernel_for<7, EXTRAS>(S);
-    case 8: return multi_kernel_for<8, EXTRAS>(S);
-#endif
-    default: return nullptr;
-  }
+// k_deal: 7x7 and 8x8 boards with 9 .. 64 tiles (and targets), G = 4 or 8 lanes per board, TPL = ceil(tiles / G) tiles per lane
+SmallKernel deal_kernel(int S, int lanes, int tpl, bool extras, bool nt) {
+  return by_flag<SmallKernel>(extras, [&](auto e) {
+    return by_flag<SmallKernel>(nt, [&](auto n) {
+      return by_value<SmallKernel, 7, 8>(S, [&](auto s) {
+        return by_value<SmallKernel, 4, 8>(lanes, [&](auto g) {
+          return by_value<SmallKernel, 2, 3, 4, 5, 6, 7, 8>(tpl, [&](auto t) -> SmallKernel {
+            if constexpr (g == 8 || t >= 3) return k_deal<s, g, t, e, n>; else return nullptr;
+          });
+        });
+      });
+    });
+  });
+}
+
+// k_lines: 4 lanes per board up to 16x16 and 8 lanes with 1 or 2 tiles per lane, 16 lanes with 1 .. 16, 32 lanes above 16x16 with 1 .. 8
+LinesKernel lines_kernel(bool wide, int lpb, int tpl, bool nt, bool extras) {
+  return by_flag<LinesKernel>(wide, [&](auto w) {
+    return by_value<LinesKernel, 4, 8, 16, 32>(lpb, [&](auto l) {
+      return by_value<LinesKernel, 1, 2, 4, 8, 16>(tpl, [&](auto t) {
+        return by_flag<LinesKernel>(nt, [&](auto n) {
+          return by_flag<LinesKernel>(extras, [&](auto e) -> LinesKernel {
+            if constexpr ((l == 4 && !w && t <= 2) || (l == 8 && t <= 2) || l == 16 || (l == 32 && w && t <= 8)) return k_lines<w, l, t, n, e>;
+            else return nullptr;
+          });
+        });
+      });
+    });
+  });
+}
+
+// k_state: 8 or 16 cells in flight per lane
+LinesKernel state_kernel(bool wide, bool extras, int batch) {
+  return by_flag<LinesKernel>(wide, [&](auto w) {
+    return by_flag<LinesKernel>(extras, [&](auto e) {
+      return by_value<LinesKernel, 8, 16>(batch, [&](auto b) -> LinesKernel { return k_state<w, e, b>; });
+    });
+  });
 }
 
 // k_multi reads and writes G boards per lane with one access: the batch must be a multiple of G and every
 // state / output row G-element aligned (rows of a [T][N] array start at t * N)
 bool multi_applicable(const KArgs &a) {
-  constexpr uintptr_t G = TS_MULTI_G;
+  constexpr uintptr_t G = kMultiBoardsPerLane;
   if (a.N % (int64_t)G != 0 || a.N < g_multi_min_boards.load(std::memory_order_relaxed) || a.nt || a.onehot) return false;
   const uintptr_t bytes = (uintptr_t)a.pos | (uintptr_t)a.init | (uintptr_t)a.tgt | (uintptr_t)a.done | (uintptr_t)a.actions |
                           (uintptr_t)a.flags | (uintptr_t)a.valid;
   if ((uintptr_t)a.valid4 & (4 * G - 1)) return false;
   const uintptr_t words = (uintptr_t)a.blk | (uintptr_t)a.step_count | (uintptr_t)a.reward;
   return (bytes & (G - 1)) == 0 && (words & (4 * G - 1)) == 0;
-}
-#endif
-
-// k_deal: 7x7 and 8x8 boards with 9 .. 64 tiles (and targets), G lanes per board, TPL = ceil(tiles / G) tiles per lane
-template <int S, int G, bool EXTRAS, bool NT>
-SmallKernel deal_kernel_tpl(int tpl) {
-  switch (tpl) {
-    case 2: if constexpr (G == 8) return k_deal<S, G, 2, EXTRAS, NT>; else return nullptr;
-    case 3: return k_deal<S, G, 3, EXTRAS, NT>;
-    case 4: return k_deal<S, G, 4, EXTRAS, NT>;
-    case 5: return k_deal<S, G, 5, EXTRAS, NT>;
-    case 6: return k_deal<S, G, 6, EXTRAS, NT>;
-    case 7: return k_deal<S, G, 7, EXTRAS, NT>;
-    case 8: return k_deal<S, G, 8, EXTRAS, NT>;
-    default: return nullptr;
-  }
-}
-
-template <bool EXTRAS, bool NT>
-SmallKernel deal_kernel(int S, int lanes, int tpl) {
-  if (S == 7) return lanes == 4 ? deal_kernel_tpl<7, 4, EXTRAS, NT>(tpl) : deal_kernel_tpl<7, 8, EXTRAS, NT>(tpl);
-  if (S == 8) return lanes == 4 ? deal_kernel_tpl<8, 4, EXTRAS, NT>(tpl) : deal_kernel_tpl<8, 8, EXTRAS, NT>(tpl);
-  return nullptr;
 }
 
 inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
@@ -2476,9 +2286,9 @@ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
 // wrong twice over: the corruption had nothing to do with LDS - it is the gfx950 VGPR hazard described at the top of this
 // file (root-caused in round 3, profiles/r03_wrong_slide_isa.md), which one compiled form of k_small<8, 0, false> happened
 // to trigger.
-constexpr size_t kMaxBlockLds = TS_MAX_BLOCK_LDS;
+constexpr size_t kMaxBlockLds = 64 * 1024;
 
-// the device's own per-block limit (queried once per thread and device); 0 when the query fails
+// the device's own per-block limit (queried once per thread and device, by launch() only); 0 when the query fails
 size_t device_block_lds_limit() {
   thread_local int cached_dev = -1;
   thread_local size_t cached = 0;
@@ -2552,7 +2362,7 @@ constexpr int kEdgeCapStateBytes = 20;  // k_small forms with fewer bytes of sta
                                         // tiles at 1 GB: both 149 / 146 us, one 154 - 166, none 173 / 176; r04_large_batch_edges_small_boards*.log)
 // Block -> board-range mapping: pieces of P one-wave blocks per XCD (r04_contig_sweep.log, r04_piece_by_shape.log; eighths -> best piece:
 // cfg2 122.2 -> 118.4 us with 32, cfg4 113.9 -> 107.7 with 16, 4x4 at 4M boards 133 -> 124.5 with 64)
-constexpr uint32_t kPieceShortChunk = TS_XCD_PIECE_POLICY, kPieceLongChunk = TS_XCD_PIECE_LONG, kPieceDealt = TS_XCD_PIECE_LINES;
+constexpr uint32_t kPieceShortChunk = 64, kPieceLongChunk = 32, kPieceDealt = 16;  // (dealt: k_lines, k_deal)
 constexpr uint64_t kPieceLongFrom = 8 * KiB;
 // A cached wave in every N of a nontemporal stream (r04_cached_every_nth_wave*.log, r04_cached_every_wide_boards.log,
 // r04_cached_every_validation.log): single-stream launches up to 704 MiB; 3x3 .. 8x8 one lane per board: every 16th (6x6 -7 .. -9 %,
@@ -2605,15 +2415,11 @@ constexpr uint64_t kLinesDenseExtraMaxBytes = 1024 * MiB;
 constexpr uint32_t kPieceDenseBlocks = 24;
 // k_state: eight cells (and targets) in flight per lane up to this many tiles, sixteen above (r05_state_only_ab.log)
 constexpr int kStateBatch8MaxT = 8;
+// k_deal: a board dealt over 4 lanes up to this many tiles, over 8 above
+constexpr int kDealLanes4MaxT = 32;
 }  // namespace policy
 Residency ooc_residency(bool out_of_cache, bool lines_kernel, bool compute_heavy, uint64_t chunk, int tiles) {
-#if defined(TS_RES_ALWAYS)  // experiment: apply the forced residency to cache-resident launches too
-  (void)out_of_cache;
-  return {TS_OOC_WAVES, TS_OOC_BLOCKS};
-#endif
-  if (!out_of_cache || TS_OOC_WAVES == 0) return {0, 0};
-  if (TS_OOC_WAVES > 0) return {TS_OOC_WAVES, TS_OOC_BLOCKS > 0 ? TS_OOC_BLOCKS : 0};
-  if (compute_heavy) return {0, 0};
+  if (!out_of_cache || compute_heavy) return {0, 0};
   // Round 3: with store instructions that cover whole 128-byte lines (emit_bytes_as_f32) a launch tolerates - and wants -
   // more resident waves than before (profiles/r03_emit_edges_ab.log, r03_residency_sweep.log).
   // Round 4: re-tuned on PHYSICALLY CONTIGUOUS output buffers (the host's default beyond the Infinity Cache), which want more
@@ -2682,12 +2488,8 @@ uint32_t edge_policy_capped(uint64_t obs_chunk, uint64_t edge_instruction_sites,
 // cfg4 113.9 -> 107.7 (16), 4x4 at 4M boards 133 -> 124.5 (64).  Too small a piece loses (cfg2 with 8: 120.7), too large a one
 // approaches eighths again.
 uint32_t piece_policy(bool lines_kernel, uint64_t chunk) {
-#if TS_XCD_PIECE_POLICY >= 0
   if (lines_kernel) return policy::kPieceDealt;
   return chunk < policy::kPieceLongFrom ? policy::kPieceShortChunk : policy::kPieceLongChunk;
-#else
-  return 0u;
-#endif
 }
 
 // A sprinkle of cached stores in a nontemporal stream (round 4).  Beyond the Infinity Cache every wave streams its chunk out with
@@ -2721,13 +2523,9 @@ uint32_t cached_every_policy(int S, uint64_t output_bytes, bool two_streams) {
 // half waves (9.6 / 13.8 KB), 7x7 and 8x8 QUARTER waves (9.4 / 12.3 KB: 7x7 98.9 -> 83.2, 8x8 with 4 tiles 95.5 -> 82.8,
 // with 8 tiles 101.8 -> 82.8: 0.80 -> 0.96 of the HBM roofline).  `primary`: bytes per board of the launch's first large
 // stream (float32 observation, else uint8 observation, else one-hot planes).
-constexpr uint64_t kHugeStreamBytes = policy::kHugeStream;
 int small_boards_per_wave(bool out_of_cache, bool register_path, uint64_t primary, uint64_t state_bytes, uint64_t n_boards) {
-#if TS_SMALL_OOC_BPW > 0
-  return (out_of_cache && register_path) ? TS_SMALL_OOC_BPW : kWave;
-#else
-  if (!out_of_cache || !register_path || TS_OOC_WAVES == 0) return kWave;  // (the any-tile-count path is bound by its serial tile
-                                                                             // loops: half waves 101.8 -> 120.9 us at 6x6 / 12 tiles)
+  if (!out_of_cache || !register_path) return kWave;  // (the any-tile-count path is bound by its serial tile loops: half waves
+                                                      // 101.8 -> 120.9 us at 6x6 / 12 tiles)
   // Once the STATE of the batch no longer fits the Infinity Cache either a partial wave's short pieces of every state row cost
   // more than its shorter chunk wins (policy::kSmallFullWavesStateBytes: 4x4 at 20M boards 0.589 -> 0.751 of the roofline; at 16M
   // boards half waves still win).
@@ -2740,7 +2538,7 @@ int small_boards_per_wave(bool out_of_cache, bool register_path, uint64_t primar
   // the roofline, half waves with one contiguous eighth per XCD (piece_policy) hold 0.87 - 0.88: 7x7 at 1.3 / 1.7 GB 248.6 -> 196.6 /
   // 365.4 -> 256.6 us, 8x8 203.9 -> 195.5 / 296.9 -> 252.0 (at 1.0 GB quarter waves still win: 150 against 165;
   // profiles/r04_large_batch_probe.log).
-  if (primary >= policy::kHugeStreamMinPrimary && primary * n_boards > kHugeStreamBytes) return 32;
+  if (primary >= policy::kHugeStreamMinPrimary && primary * n_boards > policy::kHugeStream) return 32;
   // Boards up to 6x6 with 20 bytes of state per board and more (six tiles, say) want FULL waves beyond 1 GiB - fewer, wider state
   // accesses - where the two-tile forms want shorter chunks: 5x5 / 6 tiles at 1.4 GB 308.5 us with quarter waves, 218.1 with full
   // ones (0.63 -> 0.89), 4x4 / 6 tiles at 2.1 GB 522 -> 355, 6x6 / 6 tiles at 1.4 GB 248 -> 220, 6x6 / 3 tiles 225.5 -> 208.8
@@ -2750,7 +2548,6 @@ int small_boards_per_wave(bool out_of_cache, bool register_path, uint64_t primar
   for (int bpw = kWave; bpw > 16; bpw >>= 1)
     if (primary * (uint64_t)bpw <= limit) return bpw;
   return 16;
-#endif
 }
 
 // ts_dims.launch_hint: resident blocks per CU relative to the policy, only where the policy bounds them at all
@@ -2769,14 +2566,12 @@ int32_t finish_launch() {
   return TS_OK;
 }
 
-using LinesKernel = void (*)(const KArgs, const int, const uint32_t);
-
 // What one call of the hot path launches: kernel, grid, LDS request and the policy fields of KArgs - everything launch() decides,
 // computed without touching the device (plan_launch), so that ts_describe_launch can report it and a CPU test can pin it.
 struct LaunchPlan {
   KArgs a;
   SmallKernel small = nullptr;   // k_small / k_multi / k_deal
-  LinesKernel lines = nullptr;   // k_lines
+  LinesKernel lines = nullptr;   // k_lines / k_state
   int S = 0;
   uint32_t inv_s = 0;
   uint32_t blocks = 0, threads = 0;
@@ -2785,6 +2580,240 @@ struct LaunchPlan {
   int32_t family = 0, lanes_per_board = 0, boards_per_lane = 1, tiles_per_lane = 0, extras = 0, wide = 0, waves_per_block = 0, blocks_per_cu = 0;
   uint64_t output_bytes = 0, resident_bytes = 0;
 };
+
+// What a family's planner chooses besides the KArgs fields it sets; plan_launch turns it into the grid and the plan.
+struct Choice {
+  SmallKernel small = nullptr;
+  LinesKernel lines = nullptr;
+  int32_t family = TS_KERNEL_NONE, lanes_per_board = 1, boards_per_lane = 1, tiles_per_lane = 0, extras = 0, wide = 0;
+  int max_waves = kWavesPerBlock;  // waves per block, halved while the block's LDS does not fit kMaxBlockLds
+  Residency res = {0, 0};
+};
+
+// Bytes of large output one board writes: float32 observation, one-hot planes, uint8 observation
+uint64_t output_bytes_per_board(const KArgs &a, int C) {
+  return (a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull);
+}
+
+// Write-back edge stores of the kernels that deal a board over several lanes (k_deal, k_lines): the chunks of observation and
+// 8 KiB pieces of the plane stream carry edge instructions
+uint32_t dealt_edge_policy(const KArgs &a, int C, uint32_t ring_k) {
+  const uint64_t N = (uint64_t)a.N;
+  return edge_policy_capped((uint64_t)a.bpw * (a.obs ? 12ull * C : 4ull * C * a.onehot_ch),
+                            (N + a.bpw - 1) / a.bpw + (a.onehot ? N * C * a.onehot_ch / 8192u : 0u), false, ring_k);
+}
+
+struct Grid {
+  int waves;
+  size_t lds_request, lds_used;
+  uint32_t blocks;
+};
+
+// Waves per block (halved from `max_waves` while the block's LDS does not fit kMaxBlockLds), the LDS request that admits the
+// residency's blocks per CU, and the blocks that cover the batch
+int32_t plan_grid(int max_waves, uint32_t lds_wave_bytes, uint32_t boards_per_wave, const Residency &res, int64_t n_boards, Grid &g) {
+  if (lds_wave_bytes > kMaxBlockLds) return TS_ERR_LIMIT;  // cannot happen within TS_MAX_*
+  int waves = max_waves;
+  while (waves > 1 && (size_t)waves * lds_wave_bytes > kMaxBlockLds) waves >>= 1;  // (k_lines, 32x32 with one-hot: 21 KiB per wave)
+  const int64_t boards_per_block = (int64_t)waves * boards_per_wave;
+  const int64_t blocks = (n_boards + boards_per_block - 1) / boards_per_block;
+  if (blocks > 0x7fffffffLL) return TS_ERR_LIMIT;
+  g.waves = waves;
+  g.lds_used = (size_t)waves * lds_wave_bytes;
+  g.lds_request = lds_request_for_blocks_per_cu(g.lds_used, res.blocks_per_cu);
+  g.blocks = (uint32_t)blocks;
+  return TS_OK;
+}
+
+// k_multi: cache-resident batches of boards up to 5x5 with their cells in registers, kMultiBoardsPerLane boards per lane
+Choice plan_multi(const ts_dims *d, int tfix, KArgs &a) {
+  const int C = d->size * d->size;
+  Choice c;
+  c.extras = a.valid || a.valid4 || a.reward;
+  c.small = multi_kernel(d->size, tfix, c.extras);
+  c.family = TS_KERNEL_MULTI, c.boards_per_lane = kMultiBoardsPerLane, c.tiles_per_lane = tfix;
+  a.lds_wave_bytes = (a.obs || a.obs_u8) ? align16((uint32_t)(kWave * kMultiBoardsPerLane * 3 * C)) : 0u;
+  a.bpw = kWave * kMultiBoardsPerLane;
+  return c;
+}
+
+// k_deal: 7x7 / 8x8 with more than 8 tiles, a board's tiles dealt over 4 lanes (up to policy::kDealLanes4MaxT tiles) or 8;
+// ts_dims.lines_lanes / TS_TUNE_LINES_LANES = 4 / 8 force a form where it exists (4 lanes: up to 32 tiles).  Smaller boards stay
+// with one lane per board: their observation is too short for a wave of 16 boards to pay for the group shuffles (6x6 / 12 tiles
+// 78.9 us one lane, 82.8 dealt; 5x5 58.3 against 65.3 - profiles/r04_deal_ab.log).  No kernel (c.small == nullptr): k_small.
+Choice plan_deal(const ts_dims *d, uint32_t ring_k, KArgs &a) {
+  const int S = d->size, C = S * S, T = d->n_tiles, Tt = d->n_targets, maxT = T > Tt ? T : Tt;
+  int lanes = maxT <= policy::kDealLanes4MaxT ? 4 : 8;
+  if (const int64_t forced = g_lines_lanes.load(std::memory_order_relaxed); forced == 4 || forced == 8) lanes = (int)forced;
+  if (d->lines_lanes == 4 || d->lines_lanes == 8) lanes = d->lines_lanes;
+  if (maxT > 32) lanes = 8;
+  const int tpl = (maxT + lanes - 1) / lanes;
+  Choice c;
+  c.extras = a.valid || a.valid4 || a.reward || a.onehot;
+  c.small = deal_kernel(S, lanes, tpl, c.extras, a.nt);
+  if (!c.small) return c;
+  c.family = TS_KERNEL_DEAL, c.lanes_per_board = lanes, c.tiles_per_lane = tpl;
+  const int bpw = kWave / lanes;
+  a.oh_boards = 0;
+  a.bpw = (uint32_t)bpw;
+  a.lds_stage_off = align16((uint32_t)(bpw * 3 * C));
+  a.lds_oh_off = align16(a.lds_stage_off + ((a.reward && !d->multi_color) ? (uint32_t)(bpw * Tt) : 0u));
+  a.lds_wave_bytes = a.lds_oh_off + (a.onehot ? 8192u : 0u);
+  // full occupancy (4-wave blocks, as many as fit): the group shuffles and the slides are a latency chain per wave, and a
+  // wave writes only 6 .. 12 KB - 8x8 / 12 tiles: 91.7 us with the large-board kernel's bound of 14 blocks per CU, 75.2 without
+  c.res = ooc_residency(a.nt != 0, true, true, (uint64_t)bpw * output_bytes_per_board(a, C), T);
+  apply_launch_hint(c.res, d->launch_hint);
+  if (a.emit_edges == 0xffu) a.emit_edges = dealt_edge_policy(a, C, ring_k);
+  if (a.xcd_piece == 0xffffffffu) a.xcd_piece = piece_policy(true, 0);
+  a.cached_every = a.nt ? cached_every_policy(0, 0, true) : 0u;  // k_deal: only when forced (8x8 with 12 tiles -1 %, with 20 tiles 0)
+  if (c.res.waves_per_block > 0) c.max_waves = c.res.waves_per_block;
+  return c;
+}
+
+// k_small: boards up to 8x8, one board per lane
+Choice plan_small(const ts_dims *d, int tfix, uint32_t ring_k, KArgs &a) {
+  const int S = d->size, C = S * S, T = d->n_tiles, Tt = d->n_targets;
+  const uint64_t N = (uint64_t)d->n_boards, out_per_board = output_bytes_per_board(a, C);
+  const uint64_t state_per_board = (uint64_t)(T + Tt + 4 * ((C + 31) / 32) + 7);  // what a step reads and writes per board
+  if (a.onehot) {  // largest power-of-two chunk of boards whose one-hot byte image fits 16 KiB
+    for (uint32_t nbc = kWave; nbc >= 4 && !a.oh_boards; nbc >>= 1)
+      if (align16(nbc * (uint32_t)(a.onehot_ch * C)) <= 16u * 1024u) a.oh_boards = nbc;
+  }
+  const bool need_masks = a.onehot && !a.oh_boards;
+  const bool need_stage = tfix == 0 || need_masks;
+  a.lds_stage_off = align16((uint32_t)(small_obs_boards(C) * 3 * C));
+  a.lds_oh_off = a.lds_stage_off + (need_stage ? align16((uint32_t)(kWave * (T + Tt))) + (need_masks ? 3u * kWave * 8u : 0u) : 0u);
+  a.lds_wave_bytes = a.lds_oh_off + align16(a.oh_boards * (uint32_t)(a.onehot_ch * C));
+  a.bpw = (uint32_t)small_boards_per_wave(a.nt != 0, tfix > 0, a.obs ? 12ull * C : a.obs_u8 ? 3ull * C : 4ull * C * a.onehot_ch,
+                                          N * state_per_board, N);
+  Choice c;
+  c.res = ooc_residency(a.nt != 0, false, tfix == 0, (uint64_t)a.bpw * out_per_board, T);
+  if (c.res.blocks_per_cu > 0 && N * state_per_board > policy::kSmallStateSpillBytes)
+    c.res.blocks_per_cu += policy::kSmallStateSpillExtraBlocks;  // the state comes from HBM too: more waves in flight to wait for it
+  // Boards up to 5x5 in the register forms, one float32 stream of up to 1 GiB: FOUR waves per block (policy::kSmallDense*) - the
+  // waves of a block share the CU's L1 for the lines of the state rows, as with the 16-lane form of k_lines.
+  bool dense_blocks = false;
+  if (c.res.blocks_per_cu > 0 && c.res.waves_per_block == 1) {
+    int w = (int)g_small_waves.load(std::memory_order_relaxed);
+    const bool policy_says = tfix > 0 && S <= policy::kSmallDenseMaxS && a.obs && !a.onehot && out_per_board * N <= policy::kSmallDenseMaxBytes;
+    if (w == 0 && policy_says) w = policy::kSmallDenseWaves, dense_blocks = true;
+    if (w == 2 || w == 4) {
+      c.res.waves_per_block = w;
+      c.res.blocks_per_cu = (c.res.blocks_per_cu + w - 1) / w + (dense_blocks ? policy::kSmallDenseExtraBlocks : 0);
+    }
+  }
+  if (a.emit_edges == 0xffu) {
+    const uint64_t chunk = (uint64_t)a.bpw * (a.obs ? 12ull * C : 4ull * C * a.onehot_ch);
+    const uint64_t sites = (N + a.bpw - 1) / a.bpw * ((a.obs && a.onehot) ? 2u : 1u);
+    a.emit_edges = (state_per_board >= (uint64_t)policy::kEdgeCapStateBytes || ring_k >= 2) ? edge_policy_capped(chunk, sites, true, ring_k) : edge_policy(chunk);
+  }
+  if (a.xcd_piece == 0xffffffffu && dense_blocks) a.xcd_piece = policy::kPieceSmallDenseBlocks;
+  if (a.xcd_piece == 0xffffffffu)  // (streams beyond ~1.2 GiB in chunks of 16 KB and more - 7x7 / 8x8 half waves: eighths, see small_boards_per_wave)
+    a.xcd_piece = ((uint64_t)a.bpw * out_per_board >= policy::kEighthsChunk && out_per_board * N > policy::kHugeStream) ? 0u : piece_policy(false, (uint64_t)a.bpw * out_per_board);
+  a.cached_every = a.nt ? cached_every_policy(S, out_per_board * N, a.onehot != nullptr) : 0u;
+  apply_launch_hint(c.res, d->launch_hint);
+  if (c.res.waves_per_block > 0) c.max_waves = c.res.waves_per_block;
+  c.extras = a.valid || a.valid4 || a.reward || a.onehot;
+  c.small = small_kernel(S, tfix, c.extras, a.nt);
+  c.family = TS_KERNEL_SMALL, c.tiles_per_lane = tfix;
+  return c;
+}
+
+// k_state: boards above 8x8 with no image to build, one board per lane.  (The single-colour reward - the nearest target of every
+// tile - stays with k_lines, which stages a board's target cells in LDS.)
+Choice plan_state(const ts_dims *d, KArgs &a) {
+  const int T = d->n_tiles, Tt = d->n_targets;
+  Choice c;
+  c.wide = d->size > 16;
+  c.extras = a.valid || a.valid4 || a.reward;
+  a.bpw = kWave;
+  a.nt = 0u;
+  a.lds_wave_bytes = (uint32_t)((c.wide ? 4 : 2) * (c.wide ? 32 : 16) * kWave * 4);  // 8 KiB, 32 KiB above 16x16
+  c.max_waves = c.wide ? 2 : 4;
+  // cells (and targets) a lane has in flight per round trip: 8 up to 8 tiles - the slots beyond a board's tiles are loads like
+  // any other (9x9 / 4 tiles, 1M boards: ts_is_won 15.7 us with 16 slots, 8.3 with 8) - else 16 (15x15 / 32 tiles: the step 24.7
+  // against 28.4 us; 32 slots cost a wave per SIMD and are slower everywhere): profiles/r05_state_only_ab.log
+  c.tiles_per_lane = (T > Tt ? T : Tt) <= policy::kStateBatch8MaxT ? 8 : 16;
+  c.lines = state_kernel(c.wide, c.extras, c.tiles_per_lane);
+  c.family = TS_KERNEL_STATE;
+  return c;
+}
+
+// k_lines: boards above 8x8 (step / reset / encode, + legality mask, reward, one-hot) with the level's precomputed line masks
+Choice plan_lines(const ts_dims *d, uint32_t ring_k, KArgs &a) {
+  const int S = d->size, C = S * S, T = d->n_tiles, Tt = d->n_targets, maxT = T > Tt ? T : Tt;
+  const bool wide = S > 16;
+  // Lanes per board: 16 lanes (4 boards per wave) only pay when there are tiles to deal over them and a wave's chunk of
+  // output is not tiny; 4 lanes exist up to 16x16 only (above, four lanes would own eight lines each and a wave's image
+  // would not fit its LDS carve).  ts_dims.lines_lanes / ts_tuning(TS_TUNE_LINES_LANES) force a form.
+  // profiles/r03_lines_lanes_ab.log: 9x9 96 -> 89 us with 4 lanes, 10x10 / 5 tiles 83 -> 77 with 8; from 12x12 on the
+  // 16-lane form wins again (its chunk per wave is already 7 KB and more), above 16x16 always
+  // Round 4, on physically contiguous output buffers (profiles/r04_lines_lanes_sweep.log, r04_lines_bpw_sweep.log): 8 lanes win up
+  // to 13x13 (11x11 94.0 -> 85.6 us, 12x12 97.4 -> 87.7, 13x13 91.0 -> 82.2); from 20x20 on a wave's chunk of four boards
+  // (19 .. 49 KB) is what limits the launch - the store-only probe writes private 49,152-B chunks at 5.8 TB/s at best and
+  // 12,288-B chunks at 7.5 (profiles/r04_big_chunk_probe.log) - so a board gets 32 lanes, one line each, and a wave two boards.
+  int lpb = 16;
+  if (S <= policy::kLines8MaxS && maxT <= policy::kLines8MaxT) lpb = 8;
+  if (S <= policy::kLines4MaxS && maxT <= policy::kLines4MaxT) lpb = 4;
+  if (S >= policy::kLines32MinS) lpb = 32;
+  if (const int64_t forced = g_lines_lanes.load(std::memory_order_relaxed); forced == 4 || forced == 8 || forced == 16 || forced == 32) lpb = (int)forced;
+  if (d->lines_lanes >= 4) lpb = d->lines_lanes;
+  if (lpb == 4 && wide) lpb = 8;
+  if (lpb == 32 && (!wide || (S & 1))) lpb = 16;  // (two boards of an odd size per wave would start odd waves' chunks off a 16-byte boundary)
+  if (lpb < 16 && (maxT + lpb - 1) / lpb > 2) lpb = 16;  // instantiated: 1 or 2 tiles per lane for 4 and 8 lanes per board
+  const int bpw_max = kWave / lpb;
+  const int per_lane = (maxT + lpb - 1) / lpb;
+  int tpl = 1;
+  while (tpl < per_lane) tpl <<= 1;
+  const int nln = wide ? 32 : 16;
+  a.lds_stage_off = align16((uint32_t)(bpw_max * 3 * C));
+  a.lds_oh_off = a.lds_stage_off + (uint32_t)(bpw_max * nln * ((wide ? 2 : 1) + 1 + 1) * 4) +
+                 (a.reward && !d->multi_color ? align16((uint32_t)(bpw_max * Tt * 2)) : 0u);
+  a.lds_wave_bytes = align16(a.lds_oh_off) + (a.onehot ? 8192u : 0u);
+  a.lds_oh_off = align16(a.lds_oh_off);
+  a.bpw = (uint32_t)bpw_max;
+  // 28x28 and up with few tiles, beyond the Infinity Cache: ONE board per wave (the upper 32 lanes idle through the slide and
+  // stream the image out with the others) - a wave's chunk is then 9.4 .. 12.3 KB instead of 18.8 .. 24.6: 28x28 / 8 tiles
+  // 92.2 -> 79.9 us, 32x32 / 4 tiles 91.1 -> 81.3; with 32 tiles the slide's idle lanes cost what the shorter chunk wins
+  // (87.8 -> 91.4: stays at two).  profiles/r04_lines_bpw_sweep_32lanes.log
+  if (a.nt && lpb == 32 && S >= policy::kLinesOneBoardMinS && maxT <= policy::kLinesOneBoardMaxT) a.bpw = 1;  // (S is even here: 12 * C is a multiple of 16)
+  // Four lanes per board (9x9 / 10x10 with at most four tiles): sixteen boards are a chunk of 15.6 / 19.2 KB - the chunk rule of the
+  // other kernels (9 .. 14 KB per wave) gives twelve boards at 9x9 and eight at 10x10: 9x9 / 4 tiles at 528 MB 79.7 -> 77.0 us,
+  // one tile 77.4 -> 74.2; 10x10 with four lanes 89.3 -> 81.3 (profiles/r05_lines_bpw_probe.log)
+  // - up to 640 MiB per launch: at 2.1 GB, where the state of 9x9 boards no longer fits the cache, twelve boards cost 15 % against
+  // sixteen (475 against 404 - 416 us: fewer, wider state reads win there)
+  if (a.nt && a.obs && lpb == 4 && 12ull * C * (uint64_t)d->n_boards <= policy::kLinesChunkRuleMaxBytes)
+    for (const int b : {16, 12, 8})
+      if (12ull * C * b <= policy::kSmallChunkMax && (3 * C * b) % 4 == 0) {
+        a.bpw = (uint32_t)b;
+        break;
+      }
+  // (a wave's chunk of float32 output must start on a 16-byte boundary: 12 * C * bpw % 16 == 0)
+  if (const int64_t forced = g_lines_bpw.load(std::memory_order_relaxed); forced >= 1 && forced <= bpw_max && (3 * C * forced) % 4 == 0) a.bpw = (uint32_t)forced;
+  const uint64_t out_per_board = output_bytes_per_board(a, C);
+  Choice c;
+  c.res = ooc_residency(a.nt != 0, true, false, (uint64_t)a.bpw * out_per_board, T);
+  bool dense_blocks = false;  // several waves per block beyond the cache (lines_waves_policy)
+  if (c.res.blocks_per_cu > 0) {
+    const int w = lines_waves_policy(lpb, a.obs != nullptr && a.onehot == nullptr);
+    if (w > 1) {
+      c.res.waves_per_block = w;
+      c.res.blocks_per_cu = (c.res.blocks_per_cu + w - 1) / w;
+      if (T + Tt >= policy::kLinesDenseRows && 12ull * C * (uint64_t)d->n_boards <= policy::kLinesDenseExtraMaxBytes) c.res.blocks_per_cu += policy::kLinesDenseExtraBlocks;
+      dense_blocks = true;
+    }
+  }
+  apply_launch_hint(c.res, d->launch_hint);
+  if (a.emit_edges == 0xffu) a.emit_edges = dealt_edge_policy(a, C, ring_k);
+  if (a.xcd_piece == 0xffffffffu) a.xcd_piece = dense_blocks ? policy::kPieceDenseBlocks : piece_policy(true, 0);
+  a.cached_every = a.nt ? cached_every_policy(S, (uint64_t)d->n_boards * out_per_board, a.onehot != nullptr) : 0u;
+  c.max_waves = (c.res.waves_per_block > 0 && c.res.waves_per_block <= kLinesWaves) ? c.res.waves_per_block : kLinesWaves;
+  c.extras = a.valid || a.valid4 || a.reward || a.onehot;
+  c.wide = wide;
+  c.lines = lines_kernel(wide, lpb, tpl, a.nt, c.extras);
+  c.family = TS_KERNEL_LINES, c.lanes_per_board = lpb, c.tiles_per_lane = tpl;
+  return c;
+}
 
 // The one launch path behind ts_reset / ts_step / ts_encode / ts_valid_moves / ...: plan_launch decides, launch() launches.
 int32_t plan_launch(const ts_dims *d, const ts_state *st, KArgs a, LaunchPlan &plan) {
@@ -2809,14 +2838,11 @@ int32_t plan_launch(const ts_dims *d, const ts_state *st, KArgs a, LaunchPlan &p
   a.mc = d->multi_color;
   a.max_steps = d->max_steps;
   a.onehot_ch = onehot_channels(d);
-  {
-    const uint64_t per_board = (a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull);
-    plan.output_bytes = per_board * (uint64_t)d->n_boards;
-    // classified by what successive launches keep rewriting (ts_dims.ring_bytes: an observation ring of k buffers), when the
-    // caller says so: a launch with no large output stays what it is
-    plan.resident_bytes = plan.output_bytes && (uint64_t)d->ring_bytes > plan.output_bytes ? (uint64_t)d->ring_bytes : plan.output_bytes;
-    a.nt = plan.resident_bytes > (uint64_t)g_nt_threshold_bytes.load(std::memory_order_relaxed) ? 1u : 0u;
-  }
+  plan.output_bytes = output_bytes_per_board(a, C) * (uint64_t)d->n_boards;
+  // classified by what successive launches keep rewriting (ts_dims.ring_bytes: an observation ring of k buffers), when the
+  // caller says so: a launch with no large output stays what it is
+  plan.resident_bytes = plan.output_bytes && (uint64_t)d->ring_bytes > plan.output_bytes ? (uint64_t)d->ring_bytes : plan.output_bytes;
+  a.nt = plan.resident_bytes > (uint64_t)g_nt_threshold_bytes.load(std::memory_order_relaxed) ? 1u : 0u;
   // Buffers of the ring the launch writes into (1 = no ring): the write-back edge stores of k alternating buffers keep k times their
   // bytes alive in the cache (edge_policy_capped)
   const uint32_t ring_k = (uint32_t)(plan.output_bytes ? (plan.resident_bytes + plan.output_bytes - 1) / plan.output_bytes : 1u);
@@ -2824,272 +2850,35 @@ int32_t plan_launch(const ts_dims *d, const ts_state *st, KArgs a, LaunchPlan &p
   if (a.nt) {
     const int64_t piece = g_xcd_piece.load(std::memory_order_relaxed);
     a.xcd_piece = d->xcd_piece == 1 ? 0u : d->xcd_piece > 1 ? (uint32_t)d->xcd_piece
-                  : piece <= 0x7fffffff ? (uint32_t)piece : 0xffffffffu;  // 0xffffffff: by kernel, below
+                  : piece <= 0x7fffffff ? (uint32_t)piece : 0xffffffffu;  // 0xffffffff: by kernel, in the planner
     const int64_t forced = g_emit_edges.load(std::memory_order_relaxed);
-    a.emit_edges = d->emit_edges > 0 ? (uint32_t)(d->emit_edges - 1) : forced >= 0 && forced <= 3 ? (uint32_t)forced : 0xffu;  // 0xff: by shape, below
+    a.emit_edges = d->emit_edges > 0 ? (uint32_t)(d->emit_edges - 1) : forced >= 0 && forced <= 3 ? (uint32_t)forced : 0xffu;  // 0xff: by shape, in the planner
   }
 
+  Choice c;
   if (S <= 8) {
-    const int tfix = (T == Tt && T >= 1 && T <= TS_MAX_TFIX && T <= C) ? T : 0;  // cells in registers
-    if (a.onehot) {  // largest power-of-two chunk of boards whose one-hot byte image fits 16 KiB
-      for (uint32_t nbc = kWave; nbc >= 4 && !a.oh_boards; nbc >>= 1)
-        if (align16(nbc * (uint32_t)(a.onehot_ch * C)) <= 16u * 1024u) a.oh_boards = nbc;
-    }
-#if TS_MULTI_G > 0
-    if (S >= 2 && S <= 5 && tfix > 0 && multi_applicable(a)) {  // cache-resident: G boards per lane
-      const bool extras = a.valid || a.valid4 || a.reward;
-      SmallKernel k = extras ? multi_kernel<true>(S, tfix) : multi_kernel<false>(S, tfix);
-      a.lds_wave_bytes = (a.obs || a.obs_u8) ? align16((uint32_t)(kWave * TS_MULTI_G * 3 * C)) : 0u;
-      a.bpw = kWave * TS_MULTI_G;
-      int waves = TS_WAVES_PER_BLOCK;
-      while (waves > 1 && (size_t)waves * a.lds_wave_bytes > kMaxBlockLds) waves >>= 1;
-      const int64_t boards_per_block = (int64_t)waves * a.bpw;
-      const int64_t blocks = (d->n_boards + boards_per_block - 1) / boards_per_block;
-      plan.small = k, plan.blocks = (uint32_t)blocks, plan.threads = (uint32_t)(waves * kWave);
-      plan.lds_request = plan.lds_used = (size_t)waves * a.lds_wave_bytes;
-      plan.family = TS_KERNEL_MULTI, plan.lanes_per_board = 1, plan.boards_per_lane = TS_MULTI_G, plan.tiles_per_lane = tfix;
-      plan.extras = extras, plan.waves_per_block = waves;
-      plan.a = a;
-      return TS_OK;
-    }
-#endif
+    const int tfix = (T == Tt && T >= 1 && T <= 8 && T <= C) ? T : 0;  // cells in registers (k_small / k_multi: up to 8 tiles)
     const int maxT = T > Tt ? T : Tt;
-    if (tfix == 0 && S >= 7 && maxT > 8 && maxT <= 64 && g_deal_enabled.load(std::memory_order_relaxed) != 0) {
-      // 7x7 / 8x8 with more than 8 tiles: a board's tiles dealt over 4 lanes (up to TS_DEAL_LANES4_MAX tiles) or 8 (k_deal);
-      // ts_dims.lines_lanes / TS_TUNE_LINES_LANES = 4 / 8 force a form where it exists (4 lanes: up to 32 tiles).  Smaller
-      // boards stay with one lane per board: their observation is too short for a wave of 16 boards to pay for the group
-      // shuffles (6x6 / 12 tiles 78.9 us one lane, 82.8 dealt; 5x5 58.3 against 65.3 - profiles/r04_deal_ab.log)
-      int lanes = maxT <= TS_DEAL_LANES4_MAX ? 4 : 8;
-      if (const int64_t forced = g_lines_lanes.load(std::memory_order_relaxed); forced == 4 || forced == 8) lanes = (int)forced;
-      if (d->lines_lanes == 4 || d->lines_lanes == 8) lanes = d->lines_lanes;
-      if (maxT > 32) lanes = 8;
-      const int tpl = (maxT + lanes - 1) / lanes;
-      const bool extras = a.valid || a.valid4 || a.reward || a.onehot;
-      SmallKernel k = extras ? (a.nt ? deal_kernel<true, true>(S, lanes, tpl) : deal_kernel<true, false>(S, lanes, tpl))
-                             : (a.nt ? deal_kernel<false, true>(S, lanes, tpl) : deal_kernel<false, false>(S, lanes, tpl));
-      if (k) {
-        const int bpw = kWave / lanes;
-        a.oh_boards = 0;
-        a.bpw = (uint32_t)bpw;
-        a.lds_stage_off = align16((uint32_t)(bpw * 3 * C));
-        a.lds_oh_off = align16(a.lds_stage_off + ((a.reward && !d->multi_color) ? (uint32_t)(bpw * Tt) : 0u));
-        a.lds_wave_bytes = a.lds_oh_off + (a.onehot ? 8192u : 0u);
-        const uint64_t out_pb = (a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull);
-        // full occupancy (4-wave blocks, as many as fit): the group shuffles and the slides are a latency chain per wave, and a
-        // wave writes only 6 .. 12 KB - 8x8 / 12 tiles: 91.7 us with the large-board kernel's bound of 14 blocks per CU, 75.2 without
-        Residency res = ooc_residency(a.nt != 0, true, true, (uint64_t)bpw * out_pb, T);
-        apply_launch_hint(res, d->launch_hint);
-        if (a.emit_edges == 0xffu)  // chunks (and 8 KiB pieces of the plane stream) that carry edge instructions
-          a.emit_edges = edge_policy_capped((uint64_t)bpw * (a.obs ? 12ull * C : 4ull * C * a.onehot_ch),
-                                                ((uint64_t)d->n_boards + bpw - 1) / bpw + (a.onehot ? (uint64_t)d->n_boards * C * a.onehot_ch / 8192u : 0u), false, ring_k);
-        if (a.xcd_piece == 0xffffffffu) a.xcd_piece = piece_policy(true, 0);
-        a.cached_every = a.nt ? cached_every_policy(0, 0, true) : 0u;  // k_deal: only when forced (8x8 with 12 tiles -1 %, with 20 tiles 0)
-        int waves = res.waves_per_block > 0 ? res.waves_per_block : TS_WAVES_PER_BLOCK;
-        while (waves > 1 && (size_t)waves * a.lds_wave_bytes > kMaxBlockLds) waves >>= 1;
-        const size_t lds_request = lds_request_for_blocks_per_cu((size_t)waves * a.lds_wave_bytes, res.blocks_per_cu);
-        const int64_t boards_per_block = (int64_t)waves * bpw;
-        const int64_t blocks = (d->n_boards + boards_per_block - 1) / boards_per_block;
-        if (blocks > 0x7fffffffLL) return TS_ERR_LIMIT;
-        plan.small = k, plan.blocks = (uint32_t)blocks, plan.threads = (uint32_t)(waves * kWave);
-        plan.lds_request = lds_request, plan.lds_used = (size_t)waves * a.lds_wave_bytes;
-        plan.family = TS_KERNEL_DEAL, plan.lanes_per_board = lanes, plan.tiles_per_lane = tpl, plan.extras = extras;
-        plan.waves_per_block = waves, plan.blocks_per_cu = res.blocks_per_cu;
-        plan.a = a;
-        return TS_OK;
-      }
-    }
-    const bool need_masks = a.onehot && !a.oh_boards;
-    const bool need_stage = tfix == 0 || need_masks;
-    a.lds_stage_off = align16((uint32_t)(small_obs_boards(C, tfix == 0) * 3 * C));
-    a.lds_oh_off = a.lds_stage_off + (need_stage ? align16((uint32_t)(kWave * (T + Tt))) + (need_masks ? 3u * kWave * 8u : 0u) : 0u);
-    a.lds_wave_bytes = a.lds_oh_off + align16(a.oh_boards * (uint32_t)(a.onehot_ch * C)) + TS_SMALL_LDS_PAD;
-    const uint64_t out_per_board = (a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull);
-    a.bpw = (uint32_t)small_boards_per_wave(a.nt != 0, tfix > 0, a.obs ? 12ull * C : a.obs_u8 ? 3ull * C : 4ull * C * a.onehot_ch,
-                                            (uint64_t)d->n_boards * (uint64_t)(T + Tt + 4 * ((C + 31) / 32) + 7), (uint64_t)d->n_boards);
-    Residency res = ooc_residency(a.nt != 0, false, tfix == 0, (uint64_t)a.bpw * out_per_board, T);
-    if (res.blocks_per_cu > 0 && (uint64_t)d->n_boards * (uint64_t)(T + Tt + 4 * ((C + 31) / 32) + 7) > policy::kSmallStateSpillBytes)
-      res.blocks_per_cu += policy::kSmallStateSpillExtraBlocks;  // the state comes from HBM too: more waves in flight to wait for it
-    // Boards up to 5x5 in the register forms, one float32 stream of up to 1 GiB: FOUR waves per block (policy::kSmallDense*) - the
-    // waves of a block share the CU's L1 for the lines of the state rows, as with the 16-lane form of k_lines.
-    bool dense_blocks = false;
-    if (res.blocks_per_cu > 0 && res.waves_per_block == 1) {
-      int w = (int)g_small_waves.load(std::memory_order_relaxed);
-      const bool policy_says = tfix > 0 && S <= policy::kSmallDenseMaxS && a.obs && !a.onehot && out_per_board * (uint64_t)d->n_boards <= policy::kSmallDenseMaxBytes;
-      if (w == 0 && policy_says) w = policy::kSmallDenseWaves, dense_blocks = true;
-      if (w == 2 || w == 4) {
-        res.waves_per_block = w;
-        res.blocks_per_cu = (res.blocks_per_cu + w - 1) / w + (dense_blocks ? policy::kSmallDenseExtraBlocks : 0);
-      }
-    }
-    if (a.emit_edges == 0xffu) {
-      const uint64_t chunk = (uint64_t)a.bpw * (a.obs ? 12ull * C : 4ull * C * a.onehot_ch);
-      const uint64_t sites = ((uint64_t)d->n_boards + a.bpw - 1) / a.bpw * ((a.obs && a.onehot) ? 2u : 1u);
-      a.emit_edges = (T + Tt + 4 * ((C + 31) / 32) + 7 >= policy::kEdgeCapStateBytes || ring_k >= 2) ? edge_policy_capped(chunk, sites, true, ring_k) : edge_policy(chunk);
-    }
-    if (a.xcd_piece == 0xffffffffu && dense_blocks) a.xcd_piece = policy::kPieceSmallDenseBlocks;
-    if (a.xcd_piece == 0xffffffffu)  // (streams beyond ~1.2 GiB in chunks of 16 KB and more - 7x7 / 8x8 half waves: eighths, see small_boards_per_wave)
-      a.xcd_piece = ((uint64_t)a.bpw * out_per_board >= policy::kEighthsChunk && out_per_board * (uint64_t)d->n_boards > kHugeStreamBytes) ? 0u : piece_policy(false, (uint64_t)a.bpw * out_per_board);
-    a.cached_every = a.nt ? cached_every_policy(S, out_per_board * (uint64_t)d->n_boards, a.onehot != nullptr) : 0u;
-    apply_launch_hint(res, d->launch_hint);
-    int waves = res.waves_per_block > 0 ? res.waves_per_block : TS_WAVES_PER_BLOCK;
-    while (waves > 1 && (size_t)waves * a.lds_wave_bytes > kMaxBlockLds) waves >>= 1;
-    if (a.lds_wave_bytes > kMaxBlockLds) return TS_ERR_LIMIT;  // cannot happen within TS_MAX_*
-    if (const size_t lim = device_block_lds_limit(); lim && (size_t)waves * a.lds_wave_bytes > lim) return TS_ERR_LIMIT;
-    const size_t lds_request = lds_request_for_blocks_per_cu((size_t)waves * a.lds_wave_bytes, res.blocks_per_cu);
-    const int64_t boards_per_block = (int64_t)waves * a.bpw;
-    const int64_t blocks = (d->n_boards + boards_per_block - 1) / boards_per_block;
-    if (blocks > 0x7fffffffLL) return TS_ERR_LIMIT;
-    const bool extras = a.valid || a.valid4 || a.reward || a.onehot;
-    SmallKernel k = extras ? (a.nt ? small_kernel<true, true>(S, tfix) : small_kernel<true, false>(S, tfix))
-                           : (a.nt ? small_kernel<false, true>(S, tfix) : small_kernel<false, false>(S, tfix));
-    plan.small = k, plan.blocks = (uint32_t)blocks, plan.threads = (uint32_t)(waves * kWave);
-    plan.lds_request = lds_request, plan.lds_used = (size_t)waves * a.lds_wave_bytes;
-    plan.family = TS_KERNEL_SMALL, plan.lanes_per_board = 1, plan.tiles_per_lane = tfix, plan.extras = extras;
-    plan.waves_per_block = waves, plan.blocks_per_cu = res.blocks_per_cu;
+    if (S >= 2 && S <= 5 && tfix > 0 && multi_applicable(a))  // cache-resident: two boards per lane
+      c = plan_multi(d, tfix, a);
+    else if (tfix == 0 && S >= 7 && maxT > 8 && maxT <= 64 && g_deal_enabled.load(std::memory_order_relaxed) != 0)
+      c = plan_deal(d, ring_k, a);
+    if (!c.small) c = plan_small(d, tfix, ring_k, a);
   } else {
     if (!st->lines) return TS_ERR_NULL;  // boards above 8x8 need the per-level tables of ts_prepare
-    if (!a.obs && !a.obs_u8 && !a.onehot && !(a.reward && !d->multi_color) && g_state_only.load(std::memory_order_relaxed) != 0) {
-      // no image to build: one board per lane (k_state).  (The single-colour reward - the nearest target of every tile - stays
-      // with k_lines, which stages a board's target cells in LDS.)
-      const bool wide = S > 16, extras = a.valid || a.valid4 || a.reward;
-      a.lines = st->lines;
-      a.bpw = kWave;
-      a.nt = 0u;
-      a.lds_wave_bytes = (uint32_t)((wide ? 4 : 2) * (wide ? 32 : 16) * kWave * 4);  // 8 KiB, 32 KiB above 16x16
-      const int waves = wide ? 2 : 4;
-      const int64_t blocks = (d->n_boards + (int64_t)waves * kWave - 1) / ((int64_t)waves * kWave);
-      if (blocks > 0x7fffffffLL) return TS_ERR_LIMIT;
-      // cells (and targets) a lane has in flight per round trip: 8 up to 8 tiles - the slots beyond a board's tiles are loads like
-      // any other (9x9 / 4 tiles, 1M boards: ts_is_won 15.7 us with 16 slots, 8.3 with 8) - else 16 (15x15 / 32 tiles: the step 24.7
-      // against 28.4 us; 32 slots cost a wave per SIMD and are slower everywhere): profiles/r05_state_only_ab.log
-      const bool b8 = (T > Tt ? T : Tt) <= policy::kStateBatch8MaxT;
-      plan.lines = wide ? (extras ? (b8 ? k_state<true, true, 8> : k_state<true, true, 16>) : (b8 ? k_state<true, false, 8> : k_state<true, false, 16>))
-                        : (extras ? (b8 ? k_state<false, true, 8> : k_state<false, true, 16>) : (b8 ? k_state<false, false, 8> : k_state<false, false, 16>));
-      plan.tiles_per_lane = b8 ? 8 : 16;
-      plan.inv_s = (uint32_t)((65536 + S - 1) / S);
-      plan.blocks = (uint32_t)blocks, plan.threads = (uint32_t)(waves * kWave);
-      plan.lds_request = plan.lds_used = (size_t)waves * a.lds_wave_bytes;
-      plan.family = TS_KERNEL_STATE, plan.lanes_per_board = 1, plan.extras = extras, plan.wide = wide, plan.waves_per_block = waves;
-      plan.a = a;
-      return TS_OK;
-    }
-    // step / reset / encode (+ legality mask, reward, one-hot) with the level's precomputed line masks: k_lines
-    const bool wide = S > 16;
     a.lines = st->lines;
-    // Lanes per board: 16 lanes (4 boards per wave) only pay when there are tiles to deal over them and a wave's chunk of
-    // output is not tiny; 4 lanes exist up to 16x16 only (above, four lanes would own eight lines each and a wave's image
-    // would not fit its LDS carve).  ts_dims.lines_lanes / ts_tuning(TS_TUNE_LINES_LANES) force a form.
-    const int maxT = T > Tt ? T : Tt;
-    // profiles/r03_lines_lanes_ab.log: 9x9 96 -> 89 us with 4 lanes, 10x10 / 5 tiles 83 -> 77 with 8; from 12x12 on the
-    // 16-lane form wins again (its chunk per wave is already 7 KB and more), above 16x16 always
-    // Round 4, on physically contiguous output buffers (profiles/r04_lines_lanes_sweep.log, r04_lines_bpw_sweep.log): 8 lanes win up
-    // to 13x13 (11x11 94.0 -> 85.6 us, 12x12 97.4 -> 87.7, 13x13 91.0 -> 82.2); from 20x20 on a wave's chunk of four boards
-    // (19 .. 49 KB) is what limits the launch - the store-only probe writes private 49,152-B chunks at 5.8 TB/s at best and
-    // 12,288-B chunks at 7.5 (profiles/r04_big_chunk_probe.log) - so a board gets 32 lanes, one line each, and a wave two boards.
-    int lpb = 16;
-    if (S <= policy::kLines8MaxS && maxT <= policy::kLines8MaxT) lpb = 8;
-    if (S <= policy::kLines4MaxS && maxT <= policy::kLines4MaxT) lpb = 4;
-    if (S >= policy::kLines32MinS) lpb = 32;
-    if (const int64_t forced = g_lines_lanes.load(std::memory_order_relaxed); forced == 4 || forced == 8 || forced == 16 || forced == 32) lpb = (int)forced;
-    if (d->lines_lanes >= 4) lpb = d->lines_lanes;
-    if (lpb == 4 && wide) lpb = 8;
-    if (lpb == 32 && (!wide || (S & 1))) lpb = 16;  // (two boards of an odd size per wave would start odd waves' chunks off a 16-byte boundary)
-    if (lpb < 16 && (maxT + lpb - 1) / lpb > 2) lpb = 16;  // instantiated: 1 or 2 tiles per lane for 4 and 8 lanes per board
-    const int bpw_max = kWave / lpb;
-    const int per_lane = (maxT + lpb - 1) / lpb;
-    int tpl = 1;
-    while (tpl < per_lane) tpl <<= 1;
-    const int nln = wide ? 32 : 16;
-    a.lds_stage_off = align16((uint32_t)(bpw_max * 3 * C));
-    const bool lines_extras = a.valid || a.valid4 || a.reward || a.onehot;
-    a.lds_oh_off = a.lds_stage_off + (uint32_t)(bpw_max * nln * ((wide ? 2 : 1) + 1 + 1) * 4) +
-                   (a.reward && !d->multi_color ? align16((uint32_t)(bpw_max * Tt * 2)) : 0u);
-    a.lds_wave_bytes = align16(a.lds_oh_off) + (a.onehot ? 8192u : 0u) + TS_LINES_LDS_PAD;
-    a.lds_oh_off = align16(a.lds_oh_off);
-    a.bpw = (a.nt && TS_LINES_OOC_BPW > 0 && TS_LINES_OOC_BPW <= bpw_max) ? TS_LINES_OOC_BPW : (uint32_t)bpw_max;
-    // 28x28 and up with few tiles, beyond the Infinity Cache: ONE board per wave (the upper 32 lanes idle through the slide and
-    // stream the image out with the others) - a wave's chunk is then 9.4 .. 12.3 KB instead of 18.8 .. 24.6: 28x28 / 8 tiles
-    // 92.2 -> 79.9 us, 32x32 / 4 tiles 91.1 -> 81.3; with 32 tiles the slide's idle lanes cost what the shorter chunk wins
-    // (87.8 -> 91.4: stays at two).  profiles/r04_lines_bpw_sweep_32lanes.log
-    if (a.nt && lpb == 32 && S >= policy::kLinesOneBoardMinS && maxT <= policy::kLinesOneBoardMaxT) a.bpw = 1;  // (S is even here: 12 * C is a multiple of 16)
-    // Four lanes per board (9x9 / 10x10 with at most four tiles): sixteen boards are a chunk of 15.6 / 19.2 KB - the chunk rule of the
-    // other kernels (9 .. 14 KB per wave) gives twelve boards at 9x9 and eight at 10x10: 9x9 / 4 tiles at 528 MB 79.7 -> 77.0 us,
-    // one tile 77.4 -> 74.2; 10x10 with four lanes 89.3 -> 81.3 (profiles/r05_lines_bpw_probe.log)
-    // - up to 640 MiB per launch: at 2.1 GB, where the state of 9x9 boards no longer fits the cache, twelve boards cost 15 % against
-    // sixteen (475 against 404 - 416 us: fewer, wider state reads win there)
-    if (a.nt && a.obs && lpb == 4 && 12ull * C * (uint64_t)d->n_boards <= policy::kLinesChunkRuleMaxBytes)
-      for (const int b : {16, 12, 8})
-        if (12ull * C * b <= policy::kSmallChunkMax && (3 * C * b) % 4 == 0) {
-          a.bpw = (uint32_t)b;
-          break;
-        }
-    // (a wave's chunk of float32 output must start on a 16-byte boundary: 12 * C * bpw % 16 == 0)
-    if (const int64_t forced = g_lines_bpw.load(std::memory_order_relaxed); forced >= 1 && forced <= bpw_max && (3 * C * forced) % 4 == 0) a.bpw = (uint32_t)forced;
-    Residency res = ooc_residency(a.nt != 0, true, false,
-                                        (uint64_t)a.bpw * ((a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull)), T);
-    bool dense_blocks = false;  // several waves per block beyond the cache (lines_waves_policy)
-    if (res.blocks_per_cu > 0) {
-      const int w = lines_waves_policy(lpb, a.obs != nullptr && a.onehot == nullptr);
-      if (w > 1) {
-        res.waves_per_block = w;
-        res.blocks_per_cu = (res.blocks_per_cu + w - 1) / w;
-        if (T + Tt >= policy::kLinesDenseRows && 12ull * C * (uint64_t)d->n_boards <= policy::kLinesDenseExtraMaxBytes) res.blocks_per_cu += policy::kLinesDenseExtraBlocks;
-        dense_blocks = true;
-      }
-    }
-    apply_launch_hint(res, d->launch_hint);
-    if (a.emit_edges == 0xffu)
-      a.emit_edges = edge_policy_capped((uint64_t)a.bpw * (a.obs ? 12ull * C : 4ull * C * a.onehot_ch),
-                                            ((uint64_t)d->n_boards + a.bpw - 1) / a.bpw + (a.onehot ? (uint64_t)d->n_boards * C * a.onehot_ch / 8192u : 0u), false, ring_k);
-    if (a.xcd_piece == 0xffffffffu) a.xcd_piece = dense_blocks ? policy::kPieceDenseBlocks : piece_policy(true, 0);
-    a.cached_every = a.nt ? cached_every_policy(S, (uint64_t)d->n_boards * ((a.obs ? 12ull * C : 0ull) + (a.onehot ? 4ull * C * a.onehot_ch : 0ull) + (a.obs_u8 ? 3ull * C : 0ull)),
-                                                        a.onehot != nullptr) : 0u;
-    int waves = (res.waves_per_block > 0 && res.waves_per_block <= TS_LINES_WAVES) ? res.waves_per_block : TS_LINES_WAVES;
-    while (waves > 1 && (size_t)waves * a.lds_wave_bytes > kMaxBlockLds) waves >>= 1;  // 32x32 with one-hot: 21 KiB per wave
-    if ((size_t)waves * a.lds_wave_bytes > kMaxBlockLds) return TS_ERR_LIMIT;  // cannot happen within TS_MAX_*
-    if (const size_t lim = device_block_lds_limit(); lim && (size_t)waves * a.lds_wave_bytes > lim) return TS_ERR_LIMIT;
-    const size_t lds_request = lds_request_for_blocks_per_cu((size_t)waves * a.lds_wave_bytes, res.blocks_per_cu);
-    const int64_t boards_per_block = (int64_t)waves * a.bpw;
-    const int64_t blocks = (d->n_boards + boards_per_block - 1) / boards_per_block;
-    if (blocks > 0x7fffffffLL) return TS_ERR_LIMIT;
-    const uint32_t inv_s = (uint32_t)((65536 + S - 1) / S);
-    LinesKernel k = nullptr;
-    auto pick = [&](auto lpb_c, auto tpl_c) -> LinesKernel {
-      constexpr int LPBC = decltype(lpb_c)::value, TPLC = decltype(tpl_c)::value;
-      if (lines_extras)
-        return wide ? (a.nt ? k_lines<true, (LPBC < 8 ? 8 : LPBC), TPLC, true, true> : k_lines<true, (LPBC < 8 ? 8 : LPBC), TPLC, false, true>)
-                    : (a.nt ? k_lines<false, LPBC, TPLC, true, true> : k_lines<false, LPBC, TPLC, false, true>);
-      return wide ? (a.nt ? k_lines<true, (LPBC < 8 ? 8 : LPBC), TPLC, true, false> : k_lines<true, (LPBC < 8 ? 8 : LPBC), TPLC, false, false>)
-                  : (a.nt ? k_lines<false, LPBC, TPLC, true, false> : k_lines<false, LPBC, TPLC, false, false>);
-    };
-    using std::integral_constant;
-    if (lpb == 16) {
-      switch (tpl) {
-        case 1: k = pick(integral_constant<int, 16>{}, integral_constant<int, 1>{}); break;
-        case 2: k = pick(integral_constant<int, 16>{}, integral_constant<int, 2>{}); break;
-        case 4: k = pick(integral_constant<int, 16>{}, integral_constant<int, 4>{}); break;
-        case 8: k = pick(integral_constant<int, 16>{}, integral_constant<int, 8>{}); break;
-        default: k = pick(integral_constant<int, 16>{}, integral_constant<int, 16>{}); break;
-      }
-    } else if (lpb == 32) {  // boards above 16x16 only; at most 8 tiles per lane (255 / 32)
-      auto pick32 = [&](auto tpl_c) -> LinesKernel {
-        constexpr int TPLC = decltype(tpl_c)::value;
-        if (lines_extras) return a.nt ? k_lines<true, 32, TPLC, true, true> : k_lines<true, 32, TPLC, false, true>;
-        return a.nt ? k_lines<true, 32, TPLC, true, false> : k_lines<true, 32, TPLC, false, false>;
-      };
-      k = tpl == 1 ? pick32(integral_constant<int, 1>{}) : tpl == 2 ? pick32(integral_constant<int, 2>{})
-          : tpl == 4 ? pick32(integral_constant<int, 4>{}) : pick32(integral_constant<int, 8>{});
-    } else if (lpb == 8) {
-      k = tpl == 1 ? pick(integral_constant<int, 8>{}, integral_constant<int, 1>{}) : pick(integral_constant<int, 8>{}, integral_constant<int, 2>{});
-    } else {
-      k = tpl == 1 ? pick(integral_constant<int, 4>{}, integral_constant<int, 1>{}) : pick(integral_constant<int, 4>{}, integral_constant<int, 2>{});
-    }
-    plan.lines = k, plan.inv_s = inv_s, plan.blocks = (uint32_t)blocks, plan.threads = (uint32_t)(waves * kWave);
-    plan.lds_request = lds_request, plan.lds_used = (size_t)waves * a.lds_wave_bytes;
-    plan.family = TS_KERNEL_LINES, plan.lanes_per_board = wide && lpb < 8 ? 8 : lpb, plan.tiles_per_lane = lpb == 32 && tpl > 8 ? 8 : tpl > 16 ? 16 : tpl;
-    plan.extras = lines_extras, plan.wide = wide, plan.waves_per_block = waves, plan.blocks_per_cu = res.blocks_per_cu;
+    const bool state_only = !a.obs && !a.obs_u8 && !a.onehot && !(a.reward && !d->multi_color) && g_state_only.load(std::memory_order_relaxed) != 0;
+    c = state_only ? plan_state(d, a) : plan_lines(d, ring_k, a);
   }
+  Grid g;
+  if (const int32_t rc = plan_grid(c.max_waves, a.lds_wave_bytes, a.bpw, c.res, d->n_boards, g); rc != TS_OK) return rc;
   plan.a = a;
+  plan.small = c.small, plan.lines = c.lines;
+  plan.inv_s = c.lines ? (uint32_t)((65536 + S - 1) / S) : 0u;
+  plan.blocks = g.blocks, plan.threads = (uint32_t)(g.waves * kWave);
+  plan.lds_request = g.lds_request, plan.lds_used = g.lds_used;
+  plan.family = c.family, plan.lanes_per_board = c.lanes_per_board, plan.boards_per_lane = c.boards_per_lane, plan.tiles_per_lane = c.tiles_per_lane;
+  plan.extras = c.extras, plan.wide = c.wide, plan.waves_per_block = g.waves, plan.blocks_per_cu = c.res.blocks_per_cu;
   return TS_OK;
 }
 
@@ -3097,16 +2886,27 @@ int32_t launch(const ts_dims *d, const ts_state *st, const KArgs &a, void *strea
   LaunchPlan plan;
   const int32_t rc = plan_launch(d, st, a, plan);
   if (rc != TS_OK || plan.blocks == 0) return rc;
+  if (const size_t lim = device_block_lds_limit(); lim && plan.lds_used > lim) return TS_ERR_LIMIT;
   hipStream_t hs = (hipStream_t)stream;
-  if (plan.lines) {
+  if (plan.lines)
     hipLaunchKernelGGL(plan.lines, dim3(plan.blocks), dim3(plan.threads), plan.lds_request, hs, plan.a, plan.S, plan.inv_s);
-  } else {
-#if TS_SET_LDS_ATTR
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(plan.small), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_request);
-#endif
+  else
     hipLaunchKernelGGL(plan.small, dim3(plan.blocks), dim3(plan.threads), plan.lds_request, hs, plan.a);
-  }
   return finish_launch();
+}
+
+// ts_valid_moves / ts_valid_moves4 / ts_is_won / ts_encode / ts_encode_u8 / ts_encode_onehot / ts_reward: OP_OBSERVE with the one
+// output `out` bound to KArgs::*field
+template <class T>
+int32_t observe(const ts_dims *dims, const ts_state *st, T *out, T *KArgs::*field, void *stream) {
+  const int32_t rc = check_dims(dims);
+  if (rc) return rc;
+  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
+  if (!st || !out) return TS_ERR_NULL;
+  KArgs a = {};
+  a.op = OP_OBSERVE;
+  a.*field = out;
+  return launch(dims, st, a, stream);
 }
 
 }  // namespace
@@ -3175,58 +2975,23 @@ int32_t ts_step(const ts_dims *dims, const ts_state *st, const uint8_t *actions,
 }
 
 int32_t ts_valid_moves(const ts_dims *dims, const ts_state *st, uint8_t *mask, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !mask) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.valid = mask;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, mask, &KArgs::valid, stream);
 }
 
 int32_t ts_valid_moves4(const ts_dims *dims, const ts_state *st, uint8_t *mask4, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !mask4) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.valid4 = mask4;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, mask4, &KArgs::valid4, stream);
 }
 
 int32_t ts_is_won(const ts_dims *dims, const ts_state *st, uint8_t *won, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !won) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.flags = won;  // OP_OBSERVE writes only TS_FLAG_IS_WON (= 1) or 0
-  return launch(dims, st, a, stream);
+  return observe(dims, st, won, &KArgs::flags, stream);  // OP_OBSERVE writes only TS_FLAG_IS_WON (= 1) or 0
 }
 
 int32_t ts_encode(const ts_dims *dims, const ts_state *st, float *obs, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !obs) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.obs = obs;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, obs, &KArgs::obs, stream);
 }
 
 int32_t ts_encode_u8(const ts_dims *dims, const ts_state *st, uint8_t *obs_u8, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !obs_u8) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.obs_u8 = obs_u8;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, obs_u8, &KArgs::obs_u8, stream);
 }
 
 int32_t ts_expand_u8(const uint8_t *src, float *dst, int64_t count, void *stream) {
@@ -3330,25 +3095,11 @@ int32_t ts_unpack_handoff(const ts_dims *dims, int64_t n_padded, uint32_t fields
 }
 
 int32_t ts_encode_onehot(const ts_dims *dims, const ts_state *st, float *onehot, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !onehot) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.onehot = onehot;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, onehot, &KArgs::onehot, stream);
 }
 
 int32_t ts_reward(const ts_dims *dims, const ts_state *st, int32_t *reward, void *stream) {
-  const int32_t rc = check_dims(dims);
-  if (rc) return rc;
-  if (dims->n_boards == 0) return TS_OK;  // an empty batch may carry NULL buffers
-  if (!st || !reward) return TS_ERR_NULL;
-  KArgs a = {};
-  a.op = OP_OBSERVE;
-  a.reward = reward;
-  return launch(dims, st, a, stream);
+  return observe(dims, st, reward, &KArgs::reward, stream);
 }
 
 int32_t ts_describe_launch(const ts_dims *dims, uint32_t op, uint32_t outputs_mask, ts_launch_desc *desc) {

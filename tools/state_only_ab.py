@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Round 5: A/B of k_state builds (one board per lane, launches without an image output above 8x8) - development tool.
 
-    python tools/variant_bench.py build base: b8:-DTS_STATE_BATCH=8 b32:-DTS_STATE_BATCH=32      (CPU box)
+    python tools/variant_bench.py build base: b16:-DSTATE_BATCH=16      (CPU box; a macro the working copy reads, see variant_bench.py)
     python tools/state_only_ab.py [--shapes 15,32,24,262144 ...]                                   (GPU box)
 
 For every shape: ts_is_won, ts_valid_moves, ts_valid_moves4, ts_reward and the step of an environment without observation

@@ -2,11 +2,14 @@
 """A/B harness for kernel tunables (development tool, not part of the product).
 
   build (CPU box, ships to the GPU box with the snapshot):
-      python tools/variant_bench.py build base: nt:-DTS_NT_STORE=1 u12:-DTS_EMIT_UNROLL=12
+      python tools/variant_bench.py build base: u12:-DEMIT_UNROLL=12
   run (GPU box): interleaved rounds in ONE process, per the guide's methodology rule 24
       python tools/variant_bench.py run --config cfg1 --rounds 12 --steps 100
 
-Each variant is the shipped source compiled with extra -D flags into build/variants/<name>.so.
+Each variant is the working copy's source compiled with extra -D flags into build/variants/<name>.so.  The shipped source
+reads no macro: a flag only takes effect where the working copy has been edited to read it (in the example above, a
+`kEmitUnroll` set from EMIT_UNROLL).  To A/B two versions of the source, build one, copy its .so into build/variants/
+under a second name, and build the other.
 Every variant's first step is checked bit-for-bit against the first variant's before timing.
 """
 import argparse
