@@ -3,10 +3,12 @@
 Export names follow the reference package (ref: explainrl/environment/__init__.py:13-25):
 GameState, TilerSliderEnv, TilerSliderEnvFactory, TextRender — plus the batched
 VecTilerSliderEnv that is the point of this build.  Importing the package loads nothing
-native; constructing an environment loads lib/libtiler_slider_hip.so and fails loudly
-if it is missing (no CPU fallback).
+native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
+lib/libtiler_slider_search.so, and either fails loudly if its library is missing (no CPU fallback).
 """
 from ._cabi import TilerSliderLibraryError, build_library
+from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
+from ._search_cabi import build_library as build_search_library
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
 from .gym_wrapper import GymVecTilerSlider
@@ -20,4 +22,4 @@ __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
            "VecTilerSliderEnv", "PipelinedTilerSliderEnv",
            "StepInfo", "GymVecTilerSlider", "Level", "pack_levels", "parse_board_string", "simple_level", "build_library",
-           "TilerSliderLibraryError"]
+           "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError"]

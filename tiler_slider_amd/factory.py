@@ -51,3 +51,34 @@ class TilerSliderEnvFactory:
         thread per seed.  `seeds`: integers in 0..2**32-1 (any sequence, numpy array or tensor)."""
         return VecTilerSliderEnv.from_seeds(seeds, size=size, num_tiles=num_tiles, num_obstacles=num_obstacles,
                                             multi_color=kw.pop("multi_color", False), max_steps=max_steps, **kw)
+
+    @staticmethod
+    def solvable_seeds(n, size=5, num_tiles=2, num_obstacles=3, multi_color=False, start_seed=0, min_moves=1, max_moves=None,
+                       device=None, batch_size=1 << 16):
+        """The first `n` seeds >= start_seed, ascending (uint32 NumPy array), whose create_simple_env(size, num_tiles,
+        num_obstacles, seed) level can be solved, in no fewer than `min_moves` and (if given) no more than `max_moves` moves.
+        Most random levels cannot be solved at all (one in five at 4x4 with two tiles, one in ten at the reference's default
+        shape: DESIGN.md section 11), and slides cannot be undone, so solvable levels have to be found: the seeds are turned into
+        levels (ts_generate_mt19937) and solved (ts_solve) on the device, `batch_size` seeds at a time.  The result does not
+        depend on batch_size.  Feed it to create_vec_env_from_seeds / VecTilerSliderEnv.from_seeds.  Raises ValueError when the
+        seeds run out at 2**32 first."""
+        import torch
+        from . import _search_cabi as sc
+        n, seed, batch_size = int(n), int(start_seed), max(1, int(batch_size))
+        if n < 0 or not 0 <= seed <= 2**32 - 1:
+            raise ValueError("n must be >= 0 and start_seed between 0 and 2**32 - 1")
+        depth = sc.SOLVE_MAX_DEPTH if max_moves is None else max(0, min(int(max_moves), sc.SOLVE_MAX_DEPTH))
+        found, have = [], 0
+        while have < n:
+            if seed > 2**32 - 1:
+                raise ValueError(f"only {have} of {n} seeds found below 2**32")
+            seeds = np.arange(seed, min(seed + batch_size, 2**32), dtype=np.int64)
+            env = VecTilerSliderEnv.from_seeds(seeds, size=size, num_tiles=num_tiles, num_obstacles=num_obstacles, multi_color=multi_color,
+                                               device=device, obs_dtype=None)
+            moves, _ = env.solve_bits(depth, with_best=False)
+            # (searched no deeper than max_moves: a longer optimum reads SOLVE_DEPTH, which is negative like SOLVE_NONE)
+            hit = seeds[torch.nonzero(moves >= int(min_moves)).flatten().cpu().numpy()]
+            found.append(hit)
+            have += hit.size
+            seed += batch_size
+        return (np.concatenate(found) if found else np.zeros(0, np.int64))[:n].astype(np.uint32)

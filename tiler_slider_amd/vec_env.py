@@ -695,6 +695,54 @@ class VecTilerSliderEnv:
         self._sync_if_host()
         return won.view(torch.bool)
 
+    # ------------------------------------------------------------------ solver (lib/libtiler_slider_search.so)
+    def solve(self, max_depth=64, with_best=True):
+        """Breadth-first search of every board from its CURRENT cells, on the device: one launch (include/tiler_slider_search.h:
+        ts_solve) and two small torch kernels that spread the best-move bits into bool columns.  Returns (moves, best): moves int16 [N] - 0 for a won board, else the least number of moves that wins it within
+        `max_depth`, else SOLVE_NONE (no sequence of moves wins) or SOLVE_DEPTH (not within max_depth, unexpanded states remain);
+        best bool [N, 4] - column a True where Move a starts a shortest solution (all False where moves < 1; the kernel writes one
+        byte of four bits per board, solve_bits() returns it as it is).  `done`, the step counters and max_steps play no part, and
+        no state is written.  with_best=False: (moves, None).
+        Boards up to 8x8 whose index space (S * S) ** n_tiles is at most 65,536: ValueError otherwise."""
+        moves, bits = self.solve_bits(max_depth, with_best)
+        if bits is None:
+            return moves, None
+        return moves, (bits.unsqueeze(1) >> torch.arange(4, dtype=torch.uint8, device=bits.device) & 1).to(torch.bool)
+
+    def solve_bits(self, max_depth=64, with_best=True):
+        """solve() with the kernel's raw second output: (moves int16 [N], best uint8 [N] with bit a set where Move a starts a
+        shortest solution).  One launch, nothing else."""
+        from . import _search_cabi as sc
+        self._require_open()
+        if sc.solve_states(self._dims) == 0:
+            raise ValueError(f"solve() searches boards up to {sc.SOLVE_MAX_SIZE}x{sc.SOLVE_MAX_SIZE} whose index space (size * size) ** n_tiles is at "
+                             f"most {sc.SOLVE_MAX_STATES}; {self.size}x{self.size} with {self.n_tiles} tiles is beyond that (a hash set in "
+                             "global memory would be a different kernel)")
+        if not 0 <= int(max_depth) <= sc.SOLVE_MAX_DEPTH:
+            raise ValueError(f"max_depth must be 0..{sc.SOLVE_MAX_DEPTH}")
+        moves = self._empty(self.num_envs, torch.int16)
+        best = self._empty(self.num_envs, torch.uint8) if with_best else None
+        fn = self._fns.get("ts_solve")
+        if fn is None:
+            fn = self._fns["ts_solve"] = sc.lib().ts_solve
+        with torch.cuda.device(self.device):
+            rc = fn(C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(moves), _ptr(best),
+                    torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            sc.check(rc, "ts_solve")
+        self._sync_if_host()
+        return moves, best
+
+    _LOWEST_MOVE = (255, 0, 1, 0, 2, 0, 1, 0, 3, 0, 1, 0, 2, 0, 1, 0)  # lowest set bit of a four-bit mask, 255 for none
+
+    def expert_actions(self, max_depth=64):
+        """uint8 [N]: for every board the lowest Move that starts a shortest solution (solve()), 255 where there is none - a won
+        board, an unsolvable one, one not solved within max_depth.  step() leaves a board untouched on 255 and flags it
+        `bad_action`, so the tensor can be fed to step() as it is."""
+        _, bits = self.solve_bits(max_depth)
+        lut = torch.tensor(self._LOWEST_MOVE, dtype=torch.uint8, device=bits.device)
+        return lut[bits.to(torch.int64)]
+
     # ------------------------------------------------------------------ internals
     def _info(self):
         extras = {}
