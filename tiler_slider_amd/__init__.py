@@ -4,11 +4,14 @@ Export names follow the reference package (ref: explainrl/environment/__init__.p
 GameState, TilerSliderEnv, TilerSliderEnvFactory, TextRender — plus the batched
 VecTilerSliderEnv that is the point of this build.  Importing the package loads nothing
 native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
-lib/libtiler_slider_search.so, and either fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, and each fails loudly
+if its library is missing (no CPU fallback).
 """
 from ._cabi import TilerSliderLibraryError, build_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
+from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
+from ._table_cabi import build_library as build_table_library
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
 from .gym_wrapper import GymVecTilerSlider
@@ -16,10 +19,11 @@ from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
 from .pipelined import PipelinedTilerSliderEnv
 from .render import TextRender
-from .vec_env import StepInfo, VecTilerSliderEnv
+from .vec_env import DistanceTable, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
            "VecTilerSliderEnv", "PipelinedTilerSliderEnv",
            "StepInfo", "GymVecTilerSlider", "Level", "pack_levels", "parse_board_string", "simple_level", "build_library",
-           "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError"]
+           "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError",
+           "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE"]

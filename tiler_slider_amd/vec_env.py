@@ -69,6 +69,32 @@ class StepInfo(Mapping):
         return {k: frozen[k] for k in frozen}
 
 
+class DistanceTable:
+    """What VecTilerSliderEnv.build_table() returns: `dist` uint8 [L, (size * size) ** n_tiles] on the device, one row per level
+    (include/tiler_slider_table.h: ts_table_build), and the shape it was built for - lookups refuse an environment of another."""
+
+    def __init__(self, dist, size, n_tiles, n_targets, multi_color, max_depth):
+        self.dist = dist
+        self.size, self.n_tiles, self.n_targets, self.multi_color = int(size), int(n_tiles), int(n_targets), bool(multi_color)
+        self.max_depth = int(max_depth)
+        self._complete = None
+
+    @property
+    def shape_key(self):
+        return (self.size, self.n_tiles, self.n_targets, self.multi_color)
+
+    @property
+    def complete(self):
+        """bool [L]: the row holds no TABLE_DEEP entry, so lookups on it are exactly solve()'s answers.  Computed on first use."""
+        if self._complete is None:
+            from ._table_cabi import TABLE_DEEP
+            self._complete = ~(self.dist == TABLE_DEEP).any(dim=1)
+        return self._complete
+
+    def __len__(self):
+        return self.dist.shape[0]
+
+
 class VecTilerSliderEnv:
     """N boards of one shape (size, tile count, target count, multi_color) on one GPU."""
 
@@ -742,6 +768,95 @@ class VecTilerSliderEnv:
         _, bits = self.solve_bits(max_depth)
         lut = torch.tensor(self._LOWEST_MOVE, dtype=torch.uint8, device=bits.device)
         return lut[bits.to(torch.int64)]
+
+    # ------------------------------------------------------------------ distance-to-win tables (lib/libtiler_slider_table.so)
+    def build_table(self, max_depth=252, max_bytes=4 << 30):
+        """Solve every board's LEVEL once (include/tiler_slider_table.h: ts_table_build, one launch): a DistanceTable whose `.dist`
+        is uint8 [N, (size * size) ** n_tiles] - for every placement of the tiles its least number of moves to a won board
+        (0 .. 252), TABLE_INVALID (253: not a placement), TABLE_DEEP (254: not resolved within `max_depth` rounds) or TABLE_NONE
+        (255: no sequence of moves wins).  The level - obstacles and targets - never changes, so the table stays right through
+        reset() and auto-reset; lookup(), lookup_bits() and expert_actions_from() then answer from wherever the boards stand with
+        five byte reads per board instead of a search.  Reads no tile and writes no state.
+        The table takes N * states bytes: above `max_bytes` this raises - build the table on an environment of the DISTINCT levels
+        and pass `rows=` to the lookups.  Shapes as solve(): ValueError otherwise."""
+        from . import _table_cabi as tc
+        self._require_open()
+        states = self._table_states(tc)
+        if not 0 <= int(max_depth) <= tc.TABLE_MAX_DEPTH:
+            raise ValueError(f"max_depth must be 0..{tc.TABLE_MAX_DEPTH}")
+        nbytes = self.num_envs * states
+        if nbytes > int(max_bytes):
+            raise ValueError(f"a table of {self.num_envs} boards x {states} placements takes {nbytes} bytes, above max_bytes = {int(max_bytes)}: "
+                             "build it on an environment of the distinct levels and pass rows= to lookup() / expert_actions_from()")
+        dist = torch.empty((self.num_envs, states), dtype=torch.uint8, device=self.device)
+        self._table_call(tc, "ts_table_build", C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(dist))
+        return DistanceTable(dist, self.size, self.n_tiles, self.n_targets, self.multi_color, int(max_depth))
+
+    def lookup(self, table, rows=None):
+        """(moves int16 [N], best bool [N, 4]) of the boards as they stand, read from `table` (build_table): what solve() returns
+        wherever the table is complete.  `rows` int32 [N]: board n reads table row rows[n] (default: row n) - the caller's promise
+        that the row was built for that board's level."""
+        moves, bits = self.lookup_bits(table, rows)
+        return moves, (bits.unsqueeze(1) >> torch.arange(4, dtype=torch.uint8, device=bits.device) & 1).to(torch.bool)
+
+    def lookup_bits(self, table, rows=None):
+        """lookup() with the kernel's raw second output: (moves int16 [N], best uint8 [N]), as solve_bits().  One launch, nothing else."""
+        moves, best, _ = self._lookup(table, rows, True, True, False)
+        return moves, best
+
+    def expert_actions_from(self, table, rows=None):
+        """uint8 [N]: the lowest Move that starts a shortest solution, 255 where there is none - expert_actions() read from `table`,
+        one launch, ready for step()."""
+        return self._lookup(table, rows, False, False, True)[2]
+
+    def _table_states(self, tc):
+        states = tc.table_states(self._dims)
+        if states == 0:
+            raise ValueError(f"distance tables cover boards up to 8x8 whose index space (size * size) ** n_tiles is at most 65536; "
+                             f"{self.size}x{self.size} with {self.n_tiles} tiles is beyond that")
+        return states
+
+    def _table_call(self, tc, name, *args):
+        fn = self._fns.get(name)
+        if fn is None:
+            fn = self._fns[name] = getattr(tc.lib(), name)
+        with torch.cuda.device(self.device):
+            rc = fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
+        if rc:
+            tc.check(rc, name)
+        self._sync_if_host()
+
+    def _lookup(self, table, rows, want_moves, want_best, want_action):
+        from . import _table_cabi as tc
+        self._require_open()
+        if not isinstance(table, DistanceTable):
+            raise TypeError(f"table must be a DistanceTable (build_table()), got {type(table)}")
+        states = self._table_states(tc)
+        mine = (self.size, self.n_tiles, self.n_targets, self.multi_color)
+        if table.shape_key != mine or table.dist.shape[1] != states:
+            raise ValueError(f"the table was built for (size, tiles, targets, multi colour) = {table.shape_key}, the environment is {mine}")
+        if table.dist.device != self.device:
+            raise ValueError(f"the table lives on {table.dist.device}, the environment on {self.device}")
+        n_rows = table.dist.shape[0]
+        if rows is None:
+            if n_rows != self.num_envs:
+                raise ValueError(f"the table has {n_rows} rows for {self.num_envs} boards: pass rows= (int32 [{self.num_envs}])")
+        else:
+            rows = torch.as_tensor(rows)
+            if rows.shape != (self.num_envs,) or rows.dtype == torch.bool or rows.is_floating_point():
+                raise ValueError(f"rows must be an integer tensor of shape ({self.num_envs},)")
+            if rows.dtype != torch.int32:  # a wider index must not wrap into the table: whatever lies outside becomes -1
+                rows = rows.to(self.device)
+                rows = torch.where((rows < 0) | (rows >= n_rows), torch.full_like(rows, -1), rows)
+            rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
+            if self.strict and self.num_envs and bool(((rows < 0) | (rows >= n_rows)).any()):  # a sync, as step()'s strict check
+                raise ValueError(f"rows outside the table's 0..{n_rows - 1}")
+        moves = self._empty(self.num_envs, torch.int16) if want_moves else None
+        best = self._empty(self.num_envs, torch.uint8) if want_best else None
+        action = self._empty(self.num_envs, torch.uint8) if want_action else None
+        self._table_call(tc, "ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(table.dist), n_rows, _ptr(rows),
+                         _ptr(moves), _ptr(best), _ptr(action))
+        return moves, best, action
 
     # ------------------------------------------------------------------ internals
     def _info(self):
