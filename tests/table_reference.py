@@ -10,6 +10,7 @@ on one cell it returns cells outside the board.  That no valid placement has an 
     exact(...)     int32 [N, states]: the distance of every placement, INVALID_PLACEMENT (-1) or UNREACHABLE
     cut(...)       uint8 [N, states]: the table of include/tiler_slider_table.h for a max_depth, from exact()'s answer
     table(...)     cut(exact(...))
+    lookup(...)    (moves int16, best uint8, action uint8) [N]: what ts_table_lookup reports for boards on ANY uint8 rows
 
 The stopping rule, restated on its own: with R(d) the valid placements at distance exactly d, a board stops at the first d
 with R(d) empty, and everything unresolved becomes NONE; otherwise it stops at d = max_depth with R(d) not empty, and
@@ -95,3 +96,55 @@ def to_moves(entries):
     """What ts_table_lookup reports for table entries: int16 with NONE and INVALID -> -1 (SOLVE_NONE), DEEP -> -2 (SOLVE_DEPTH)."""
     e = np.asarray(entries).astype(np.int16)
     return np.where(e <= MAX_DEPTH, e, np.where(e == DEEP, -2, -1)).astype(np.int16)
+
+
+_LOWEST_BIT = np.array([255] + [(b & -b).bit_length() - 1 for b in range(1, 16)], np.uint8)
+
+
+def is_placement(S, blk, pos):
+    """bool [N]: the cells of pos [T, N], clipped to S * S - 1, are distinct and none of them is an obstacle of blk [W, N]."""
+    blk = np.ascontiguousarray(blk, np.uint32)
+    T, N = pos.shape
+    p = np.minimum(np.asarray(pos).astype(np.int64), S * S - 1)
+    ok = np.ones(N, bool)
+    for i in range(T):
+        ok &= ((blk[p[i] >> 5, np.arange(N)] >> (p[i] & 31).astype(np.uint32)) & 1) == 0
+        for j in range(i):
+            ok &= p[i] != p[j]
+    return ok
+
+
+def lookup(orc, S, blk, pos, rows_of_table, rows=None):
+    """The rule of ts_table_lookup (include/tiler_slider_table.h) restated on NumPy, over whatever bytes it is given - a table that
+    was built or one that nobody built.  blk [W, N], pos [T, N] (any cell ids: clipped to S * S - 1), rows_of_table uint8
+    [n_rows, states]; board n reads row rows[n] (default: row n).  The board's own entry e gives moves = to_moves(e); for e in
+    1 .. 252 bit a of best is set where the entry of the placement after Move a - one OracleBatch.step per move - is e - 1;
+    action is the lowest set bit of best, 255 for none.  A board whose clipped cells are not a placement (a tile on an obstacle,
+    two tiles on one cell) or whose row lies outside the table gets -1, 0, 255 and is never handed to the oracle."""
+    blk = np.ascontiguousarray(blk, np.uint32)
+    tab = np.asarray(rows_of_table)
+    assert tab.dtype == np.uint8 and tab.ndim == 2
+    T, N = pos.shape
+    C = S * S
+    assert blk.shape[1] == N and tab.shape[1] == C ** T
+    r = np.arange(N, dtype=np.int64) if rows is None else np.asarray(rows).astype(np.int64)
+    assert r.shape == (N,)
+    p = np.minimum(np.asarray(pos).astype(np.int64), C - 1)
+    ok = (r >= 0) & (r < tab.shape[0]) & is_placement(S, blk, pos)
+    moves, best = np.full(N, -1, np.int16), np.zeros(N, np.uint8)
+    v = np.flatnonzero(ok)
+    if v.size:
+        cells = np.ascontiguousarray(p[:, v].astype(orc.cell_dtype(S)))
+        b, none = np.ascontiguousarray(blk[:, v]), np.zeros((0, v.size), orc.cell_dtype(S))   # a slide does not look at the targets
+        e = tab[r[v], index_of(S, cells)].astype(np.int64)
+        moves[v] = to_moves(e)
+        asks = (e >= 1) & (e <= MAX_DEPTH)
+        bits = np.zeros(v.size, np.uint8)
+        for a in range(4):
+            batch = orc.OracleBatch(S, False, 2**30, b, cells, none)
+            batch.step(np.full(v.size, a, np.uint8), obs=False)
+            assert (batch.pos < C).all()
+            after = tab[r[v], index_of(S, batch.pos)].astype(np.int64)
+            bits |= ((asks & (after == e - 1)).astype(np.uint8) << a).astype(np.uint8)
+        best[v] = bits
+    return moves, best, _LOWEST_BIT[best]

@@ -29,10 +29,33 @@ def _env(S, mc, blk, init, tgt, pos=None, **kw):
     return env
 
 
-def _gpu(S, mc, blk, init, tgt, pos=None, max_depth=64):
-    """(moves int16 [N], best uint8 [N]) of ts_solve, and solve()'s bool [N, 4] checked against the bits on the way."""
+def _solve_raw(env, max_depth, want=None):
+    """ts_solve through the C-ABI into buffers the test owns, each between guard bytes: prefilled with the bytewise complement of
+    the yardstick's answer `want` = (moves, best) where the caller has it - an entry the kernel skips then differs by construction
+    -, else with 77 (no answer of the library: moves 19789, best 77).  env.solve_bits() writes into torch.empty, which hands
+    back the block of the previous, equal call."""
+    import ctypes as C
+    import torch
+    from table_harness import GUARD, guarded as _guarded, payload as _payload
+    from tiler_slider_amd import _search_cabi as sc
+    n = env.num_envs
+    fill = lambda i, dt: np.full(n, 77, dt) if want is None else ~np.asarray(want[i]).astype(dt)
+    mbuf, bbuf = _guarded(torch, env.device, fill(0, np.int16)), _guarded(torch, env.device, fill(1, np.uint8))
+    rc = sc.lib().ts_solve(C.byref(env._dims), C.byref(env._state), int(max_depth), mbuf.data_ptr() + GUARD, bbuf.data_ptr() + GUARD,
+                           torch.cuda.current_stream(env.device).cuda_stream)
+    assert rc == 0, rc
+    return _payload(mbuf, np.int16, (n,)), _payload(bbuf, np.uint8, (n,))
+
+
+def _gpu(S, mc, blk, init, tgt, pos=None, max_depth=64, want=None):
+    """(moves int16 [N], best uint8 [N]) of ts_solve, and solve()'s bool [N, 4] checked against the bits on the way.  `want`: the
+    yardstick's answer where the caller has it beforehand (_solve_raw)."""
     env = _env(S, mc, blk, init, tgt, pos)
+    raw = _solve_raw(env, max_depth, want)
+    if want is not None:
+        _same(raw, want, "into the complement of the yardstick's answer")
     moves, bits = env.solve_bits(max_depth)
+    _same(raw, (moves.cpu().numpy(), bits.cpu().numpy()), "the raw call and solve_bits()")
     moves2, best4 = env.solve(max_depth)
     moves, bits = moves.cpu().numpy(), bits.cpu().numpy()
     assert moves.dtype == np.int16 and bits.dtype == np.uint8 and str(best4.dtype) == 'torch.bool' and tuple(best4.shape) == (len(moves), 4)
@@ -56,12 +79,13 @@ def test_screenshot_levels(torch_cuda, oracle):
     from tiler_slider_amd.levels import pack_levels
     total = 0
     for (S, T, mc), (ids, blk, init, tgt, want) in ref.fixture_groups(GOLDEN_DIR, pack_levels).items():
-        moves, best = _gpu(S, mc, blk, init, tgt)
+        yard = ref.solve(oracle, S, mc, blk, tgt, init)
+        moves, best = _gpu(S, mc, blk, init, tgt, want=yard)
         np.testing.assert_array_equal(moves, want, err_msg=str((S, T, mc)))
-        _same((moves, best), ref.solve(oracle, S, mc, blk, tgt, init), (S, T, mc))
+        _same((moves, best), yard, (S, T, mc))
         assert 1 <= moves.min() and moves.max() <= 15
         for depth in (0, 3, 7):
-            m, b = _gpu(S, mc, blk, init, tgt, max_depth=depth)
+            m, b = _gpu(S, mc, blk, init, tgt, max_depth=depth, want=(np.where(want <= depth, want, ref.SOLVE_DEPTH), np.where(want <= depth, yard[1], 0)))
             np.testing.assert_array_equal(m, np.where(want <= depth, want, ref.SOLVE_DEPTH))
             np.testing.assert_array_equal(b, np.where(want <= depth, best, 0))
         total += len(ids)
@@ -79,6 +103,7 @@ def test_random_levels_from_seeds(torch_cuda, oracle, S, T, K, mc, n):
     assert (want[0] >= 1).sum() >= 3 and (want[0] == ref.SOLVE_NONE).sum() >= 3, ((want[0] >= 1).sum(), (want[0] == ref.SOLVE_NONE).sum())
     env = VecTilerSliderEnv.from_seeds(seeds, size=S, num_tiles=T, num_obstacles=K, multi_color=mc, obs_dtype=None)
     np.testing.assert_array_equal(env._init.cpu().numpy(), init)
+    _same(_solve_raw(env, 64, want), want, (S, T, K, mc, "into the complement of the yardstick's answer"))
     moves, bits = env.solve_bits()
     print(f"{S}x{S} T={T} K={K} mc={mc}: solvable {(want[0] >= 1).sum()} of {n}, deepest {want[0].max()}")
     _same((moves.cpu().numpy(), bits.cpu().numpy()), want, (S, T, K, mc))
@@ -122,12 +147,13 @@ def test_hand_made_boards(torch_cuda, oracle):
         blk, init, tgt = _pack(oracle, S, levels)
         want = ref.solve(oracle, S, mc, blk, tgt, init)
         assert want[0].tolist() == lit_moves and want[1].tolist() == lit_best, (S, mc, want)   # the yardstick against the literals
-        _same(_gpu(S, mc, blk, init, tgt), want, (S, mc, levels))
+        _same(_gpu(S, mc, blk, init, tgt, want=want), want, (S, mc, levels))
         # max_depth = d - 1 stops short of a board of optimum d, max_depth = d finds it; a board whose reachable set is exhausted at
         # a depth <= max_depth reports SOLVE_NONE, before that SOLVE_DEPTH
         for depth in (0, 1, 2):
-            got = _gpu(S, mc, blk, init, tgt, max_depth=depth)
-            _same(got, ref.solve(oracle, S, mc, blk, tgt, init, max_depth=depth), (S, mc, depth))
+            shallow = ref.solve(oracle, S, mc, blk, tgt, init, max_depth=depth)
+            got = _gpu(S, mc, blk, init, tgt, max_depth=depth, want=shallow)
+            _same(got, shallow, (S, mc, depth))
             for n, d in enumerate(lit_moves):
                 if d >= 0:
                     assert got[0][n] == (d if d <= depth else DEPTH)
@@ -135,8 +161,10 @@ def test_hand_made_boards(torch_cuda, oracle):
                 assert all(g == DEPTH for g, d in zip(got[0], lit_moves) if d != 0)
     # the walled-in tile: nothing is reachable, so depth 1 already exhausts the set
     blk, init, tgt = _pack(oracle, 4, [([(0, 1), (1, 0), (3, 2), (2, 3)], [(0, 0), (3, 3)], [(3, 3), (1, 1)])])
-    assert _gpu(4, True, blk, init, tgt, max_depth=1)[0].tolist() == [NONE] and _gpu(4, True, blk, init, tgt, max_depth=0)[0].tolist() == [DEPTH]
-    assert _gpu(4, True, blk, init, tgt, max_depth=32767)[0].tolist() == [NONE]
+    lit = lambda m: (np.array([m], np.int16), np.array([0], np.uint8))   # best is 0 wherever moves < 1
+    assert _gpu(4, True, blk, init, tgt, max_depth=1, want=lit(NONE))[0].tolist() == [NONE]
+    assert _gpu(4, True, blk, init, tgt, max_depth=0, want=lit(DEPTH))[0].tolist() == [DEPTH]
+    assert _gpu(4, True, blk, init, tgt, max_depth=32767, want=lit(NONE))[0].tolist() == [NONE]
 
 
 def test_mid_episode_and_state_untouched(torch_cuda, oracle):
@@ -234,8 +262,10 @@ def test_every_compiled_form_at_occupancy(torch_cuda, oracle, name):
         tile = lambda a: np.ascontiguousarray(np.tile(a, (1, copies))[:, :n])
         env = _env(S, mc, tile(blk), tile(init), tile(tgt))
         assert _search_cabi.describe_solve(env._dims)["blocks"] * waves_per_block >= 4096
+        tiled = (np.tile(want[0], copies)[:n], np.tile(want[1], copies)[:n])
+        _same(_solve_raw(env, 64, tiled), tiled, (name, mc, "into the complement of the yardstick's answer"))
         moves, bits = env.solve_bits()
-        _same((moves.cpu().numpy(), bits.cpu().numpy()), (np.tile(want[0], copies)[:n], np.tile(want[1], copies)[:n]), (name, mc))
+        _same((moves.cpu().numpy(), bits.cpu().numpy()), tiled, (name, mc))
 
 
 def test_both_forms_agree_where_both_exist(torch_cuda, oracle):
@@ -251,7 +281,7 @@ def test_both_forms_agree_where_both_exist(torch_cuda, oracle):
             want = ref.solve(oracle, S, mc, blk, tgt, init)
             L.ts_search_tuning(sc.TUNE_WAVE_MAX_STATES, states)
             L.ts_search_tuning(sc.TUNE_WORDS_PER_LANE, wpl)
-            _same(_gpu(S, mc, blk, init, tgt), want, (S, T, states, wpl))
+            _same(_gpu(S, mc, blk, init, tgt, want=want), want, (S, T, states, wpl))
     finally:
         L.ts_search_tuning(sc.TUNE_WAVE_MAX_STATES, 8192)
         L.ts_search_tuning(sc.TUNE_WORDS_PER_LANE, 1)

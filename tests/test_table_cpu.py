@@ -286,3 +286,79 @@ def test_yardstick_start_entries_equal_the_solver_yardstick_on_seeded_levels(ora
         unresolved = (dist > depth)
         np.testing.assert_array_equal(shallow[unresolved], np.broadcast_to(np.where(deep_board[:, None], tref.DEEP, tref.NONE), dist.shape)[unresolved])
         np.testing.assert_array_equal(shallow[~unresolved], tab[~unresolved])
+
+
+def test_yardstick_lookup_at_the_start_of_the_400_screenshot_levels_is_the_recorded_optimum(oracle):
+    """table_reference.lookup against numbers already in git: from each level's start cells it reports the fixture's min_moves,
+    a best mask that is not empty, and its lowest bit as the action."""
+    import solver_reference as ref
+    import table_reference as tref
+    from tiler_slider_amd.levels import pack_levels
+    total = 0
+    for (S, T, mc), (ids, blk, init, tgt, want) in ref.fixture_groups(GOLDEN_DIR, pack_levels).items():
+        tab = tref.table(oracle, S, mc, blk, tgt, T)
+        moves, best, action = tref.lookup(oracle, S, blk, init, tab)
+        assert moves.dtype == np.int16 and best.dtype == np.uint8 and action.dtype == np.uint8
+        np.testing.assert_array_equal(moves, want, err_msg=str((S, T, mc)))
+        assert (best >= 1).all() and (best <= 15).all()
+        np.testing.assert_array_equal(action, [(int(b) & -int(b)).bit_length() - 1 for b in best])
+        # the same boards through rows=, in reverse order, and a row outside the table
+        back = np.arange(len(ids))[::-1]
+        again = tref.lookup(oracle, S, blk[:, back], init[:, back], tab, rows=back)
+        np.testing.assert_array_equal(again[0], want[back])
+        np.testing.assert_array_equal(again[1], best[back])
+        out = tref.lookup(oracle, S, blk, init, tab, rows=np.full(len(ids), len(ids)))
+        assert (out[0] == -1).all() and (out[1] == 0).all() and (out[2] == 255).all()
+        total += len(ids)
+    assert total == 400
+
+
+@pytest.mark.parametrize("S,T,K,mc,n", ((4, 2, 2, False, 40), (5, 2, 3, True, 12)))
+def test_yardstick_lookup_over_every_valid_placement_is_the_solver_yardstick(oracle, S, T, K, mc, n):
+    """Two yardsticks that share no method: the lookup over the relaxed table, and a breadth-first search (solver_reference.solve)
+    from the same cells - every valid placement of every level, moves and best."""
+    import solver_reference as ref
+    import table_reference as tref
+    blk, init, tgt = oracle.generate_mt19937(S, T, T, K, np.arange(n, dtype=np.uint32))
+    tab = tref.table(oracle, S, mc, blk, tgt, T)
+    level, state = np.nonzero(tab != tref.INVALID)
+    C = S * S
+    pos = np.stack([(state // C ** t) % C for t in range(T)]).astype(np.uint8)
+    moves, best, action = tref.lookup(oracle, S, blk[:, level], pos, tab, rows=level)
+    want = ref.solve(oracle, S, mc, blk[:, level], tgt[:, level], pos, max_depth=32767)
+    kinds = ((want[0] >= 1).sum(), (want[0] == 0).sum(), (want[0] == -1).sum())
+    print(f"{S}x{S} T={T} K={K} mc={mc}: {len(level)} placements, moves >= 1 / 0 / -1: {kinds}, deepest {want[0].max()}")
+    assert min(kinds) >= 3
+    np.testing.assert_array_equal(moves, want[0])
+    np.testing.assert_array_equal(best, want[1])
+    np.testing.assert_array_equal(action[best == 0], 255)
+    assert ((best[best != 0] >> action[best != 0]) & 1).all() and ((best[best != 0] & ((1 << action[best != 0]) - 1)) == 0).all()
+    # an invalid placement - the first tile on the second one's cell - is answered without the oracle
+    twice = pos.copy()
+    twice[0] = twice[1]
+    out = tref.lookup(oracle, S, blk[:, level], twice, tab, rows=level)
+    assert (out[0] == -1).all() and (out[1] == 0).all() and (out[2] == 255).all()
+
+
+def test_occupancy_cases_name_exactly_the_compiled_table_kernels():
+    """tests/test_gpu_table.py runs one case per kernel at 4,096 waves: its case table (tests/table_harness.py) is the code
+    object's list, no kernel without a case and no case without a kernel; the knobs of each build case really select the kernel
+    it is named after."""
+    import table_harness as th
+    from tiler_slider_amd import _table_cabi as tc
+    assert sorted(th.OCCUPANCY_CASES) == _kernel_names(tc.LIB_PATH)
+    assert len(th.OCCUPANCY_CASES) == tc.MIN_KERNELS == 23
+    before = [tc.lib().ts_table_tuning(k, -1) for k in (0, 1, 2)]
+    for name, (S, T, K, knobs) in th.OCCUPANCY_CASES.items():
+        assert f"<{S}>" in name and (S * S) ** T <= 65536
+        if "lookup" in name:
+            assert not knobs
+            continue
+        with th.knobs(knobs):
+            for n in (1021, 4349):
+                assert tc.describe_table_build(_dims(S, T, 0, n))["name"] == name
+    S, T, K, knobs = th.SUB_WAVE_CASE
+    with th.knobs(knobs):
+        d = tc.describe_table_build(_dims(S, T, 0, 4349))
+        assert (d["name"], d["boards_per_block"], d["lanes_per_board"]) == ("k_table_wave<4>", 8, 8)
+    assert [tc.lib().ts_table_tuning(k, -1) for k in (0, 1, 2)] == before
