@@ -4,10 +4,11 @@ Export names follow the reference package (ref: explainrl/environment/__init__.p
 GameState, TilerSliderEnv, TilerSliderEnvFactory, TextRender — plus the batched
 VecTilerSliderEnv that is the point of this build.  Importing the package loads nothing
 native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
-lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, and each fails loudly
-if its library is missing (no CPU fallback).
+lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
+lib/libtiler_slider_rollout.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._cabi import TilerSliderLibraryError, build_library
+from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
 from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
@@ -19,11 +20,12 @@ from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
 from .pipelined import PipelinedTilerSliderEnv
 from .render import TextRender
-from .vec_env import DistanceTable, StepInfo, VecTilerSliderEnv
+from .vec_env import DistanceTable, Rollout, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
            "VecTilerSliderEnv", "PipelinedTilerSliderEnv",
            "StepInfo", "GymVecTilerSlider", "Level", "pack_levels", "parse_board_string", "simple_level", "build_library",
            "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError",
-           "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE"]
+           "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
+           "Rollout", "build_rollout_library"]

@@ -95,6 +95,23 @@ class DistanceTable:
         return self.dist.shape[0]
 
 
+class Rollout:
+    """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
+    device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
+    last step's); act_log, flags_log uint8 [steps, N]; pos_log cell ids [steps, T, N] (the compact form ts_encode re-encodes)."""
+
+    FIELDS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags", "act_log", "flags_log", "pos_log")
+    __slots__ = FIELDS + ("steps",)
+
+    def __init__(self, steps, **tensors):
+        self.steps = int(steps)
+        for name in self.FIELDS:
+            setattr(self, name, tensors.get(name))
+
+    def __repr__(self):
+        return f"Rollout(steps={self.steps}, " + ", ".join(n for n in self.FIELDS if getattr(self, n) is not None) + ")"
+
+
 class VecTilerSliderEnv:
     """N boards of one shape (size, tile count, target count, multi_color) on one GPU."""
 
@@ -829,6 +846,93 @@ class VecTilerSliderEnv:
     def _lookup(self, table, rows, want_moves, want_best, want_action):
         from . import _table_cabi as tc
         self._require_open()
+        dist, n_rows, rows = self._check_table(table, rows)
+        moves = self._empty(self.num_envs, torch.int16) if want_moves else None
+        best = self._empty(self.num_envs, torch.uint8) if want_best else None
+        action = self._empty(self.num_envs, torch.uint8) if want_action else None
+        self._table_call(tc, "ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(dist), n_rows, _ptr(rows),
+                         _ptr(moves), _ptr(best), _ptr(action))
+        return moves, best, action
+
+    # ------------------------------------------------------------------ fused rollouts (lib/libtiler_slider_rollout.so)
+    _ROLLOUT_STATS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags")
+    _ROLLOUT_LOGS = ("act", "flags", "pos")
+
+    def rollout(self, steps, policy="random", actions=None, table=None, rows=None, epsilon=0.0, seed=0, step_index=0, board_offset=0,
+                stats=True, log=(), advance=True):
+        """`steps` steps of every board in ONE launch (include/tiler_slider_rollout.h: ts_rollout): a board is loaded once, played in
+        its lane's registers and stored once, and each action is drawn or looked up by the kernel itself.  The result is exactly
+        what `steps` rounds of ts_fill_actions / expert_actions_from / step() leave.
+          policy "given":  actions uint8 [steps, N] on the device
+                 "random": the stream of ts_fill_actions(seed, board_offset, step_index + k)
+                 "table":  the expert move of `table` (build_table(); `rows` as in lookup()), replaced by the random draw with
+                           probability `epsilon` and wherever the expert has no move
+          stats=True: wins, finished, first_win, win_moves, reward_sum, flags (False: none; or an iterable of those names)
+          log: any of "act", "flags", "pos" - the per-step logs act_log, flags_log uint8 [steps, N], pos_log [steps, T, N]
+          advance=True: the environment moves on as `steps` calls of step() would move it (state, last flags; an observation-
+                 keeping environment re-encodes its current observation once at the end).  advance=False: a playout from where the
+                 boards stand; the environment is left untouched.
+        Returns a Rollout.  Boards up to 8x8 with at most 8 tiles and 8 targets; "table" also needs the tables' index space
+        (size * size) ** n_tiles <= 65536: ValueError otherwise."""
+        from . import _rollout_cabi as rc
+        self._require_open()
+        if not self._started:
+            raise RuntimeError("Call reset() before rollout().")
+        if self.host_mapped:
+            raise ValueError("rollout needs device buffers (host_mapped=False)")
+        if policy not in rc.POLICIES:
+            raise ValueError(f"policy must be one of {sorted(rc.POLICIES)}, got {policy!r}")
+        pol = rc.POLICIES[policy]
+        if not rc.rollout_supported(self._dims, pol):
+            raise ValueError(f"rollout() plays boards up to {rc.ROLLOUT_MAX_SIZE}x{rc.ROLLOUT_MAX_SIZE} with at most {rc.ROLLOUT_MAX_TILES} tiles and "
+                             f"{rc.ROLLOUT_MAX_TILES} targets, and the table policy an index space (size * size) ** n_tiles of at most 65536; "
+                             f"{self.size}x{self.size} with {self.n_tiles} tiles and {self.n_targets} targets is beyond that")
+        steps = int(steps)
+        if not 0 <= steps <= rc.ROLLOUT_MAX_STEPS:
+            raise ValueError(f"steps must be 0..{rc.ROLLOUT_MAX_STEPS}")
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError("epsilon must be 0..1")
+        N = self.num_envs
+        cfg = rc.RolloutCfg(steps, self._mode, pol, 1 if advance else 0, None, int(seed) & (2**64 - 1), int(step_index), int(board_offset),
+                            int(round(float(epsilon) * 2**32)), None, 0, None)
+        if pol == rc.GIVEN:
+            if not (isinstance(actions, torch.Tensor) and actions.dtype == torch.uint8 and actions.device == self.device
+                    and tuple(actions.shape) == (steps, N) and actions.is_contiguous()):
+                raise TypeError(f"actions must be a contiguous uint8 device tensor of shape [{steps}, {N}]")
+            cfg.actions = _ptr(actions)
+        elif pol == rc.TABLE:
+            dist, n_rows, rows = self._check_table(table, rows)
+            cfg.table, cfg.n_rows, cfg.rows = _ptr(dist), n_rows, _ptr(rows)
+        names = self._ROLLOUT_STATS if stats is True else () if not stats else tuple(stats)
+        logs = (log,) if isinstance(log, str) else tuple(log)
+        if set(names) - set(self._ROLLOUT_STATS) or set(logs) - set(self._ROLLOUT_LOGS):
+            raise ValueError(f"stats are {self._ROLLOUT_STATS}, logs {self._ROLLOUT_LOGS}")
+        got = {name: torch.zeros(N, dtype=torch.uint8 if name == "flags" else torch.int32, device=self.device) for name in names}
+        for name in logs:
+            shape = (steps, self.n_tiles, N) if name == "pos" else (steps, N)
+            got[name + "_log"] = torch.zeros(shape, dtype=self._pos.dtype if name == "pos" else torch.uint8, device=self.device)
+        bound = dict(got)
+        if advance:  # the environment's own flag byte becomes the last step's, as after step(); a Rollout's `flags` is then that tensor
+            bound["flags"] = self._flags
+            if "flags" in got:
+                got["flags"] = self._flags
+        out = rc.RolloutOut(*(_ptr(bound.get(f)) for f in rc.OUT_FIELDS))
+        if steps and N and bound:
+            fn = self._fns.get("ts_rollout")
+            if fn is None:
+                fn = self._fns["ts_rollout"] = rc.lib().ts_rollout
+            with torch.cuda.device(self.device):
+                code = fn(C.byref(self._dims), C.byref(self._state), C.byref(cfg), C.byref(out), torch.cuda.current_stream(self.device).cuda_stream)
+            if code:
+                rc.check(code, "ts_rollout")
+            if advance and self.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful
+                self._call("ts_encode" if self.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(self._dims), C.byref(self._state),
+                           _ptr(self._obs))
+        return Rollout(steps, **got)
+
+    def _check_table(self, table, rows):
+        """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
+        from . import _table_cabi as tc
         if not isinstance(table, DistanceTable):
             raise TypeError(f"table must be a DistanceTable (build_table()), got {type(table)}")
         states = self._table_states(tc)
@@ -851,12 +955,7 @@ class VecTilerSliderEnv:
             rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
             if self.strict and self.num_envs and bool(((rows < 0) | (rows >= n_rows)).any()):  # a sync, as step()'s strict check
                 raise ValueError(f"rows outside the table's 0..{n_rows - 1}")
-        moves = self._empty(self.num_envs, torch.int16) if want_moves else None
-        best = self._empty(self.num_envs, torch.uint8) if want_best else None
-        action = self._empty(self.num_envs, torch.uint8) if want_action else None
-        self._table_call(tc, "ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(table.dist), n_rows, _ptr(rows),
-                         _ptr(moves), _ptr(best), _ptr(action))
-        return moves, best, action
+        return table.dist, n_rows, rows
 
     # ------------------------------------------------------------------ internals
     def _info(self):
