@@ -127,6 +127,28 @@ def test_handoff_layout_matches_the_host_mirror_and_arguments_are_validated():
     assert L.ts_pack_handoff(C.byref(_cabi.Dims(0, 4, 2, 2, 1, 100, 0)), None, None, None, 0, 1, None, None) == _cabi.OK  # empty shard
 
 
+def test_every_binding_lists_the_headers_its_source_includes():
+    """A library is rebuilt when its source or one of its HEADERS is newer: every quoted #include of a binding's SRC, followed
+    through the headers it reaches, must be in [SRC] + HEADERS of that binding."""
+    from cabi_harness import _bindings
+    from tiler_slider_amd import _cabi
+    csrc = os.path.dirname(os.path.realpath(_cabi.SRC))
+    for binding in _bindings():
+        listed = {os.path.realpath(p) for p in [binding.SRC] + binding.HEADERS}
+        seen, todo = set(), [os.path.realpath(binding.SRC)]
+        while todo:
+            path = todo.pop()
+            if path in seen:
+                continue
+            seen.add(path)
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+                todo.append(os.path.realpath(os.path.join(os.path.dirname(path), inc)))
+        assert seen <= listed, (binding.__name__, sorted(seen - listed))
+        # the walk found what is known to be included: ts_core.h by all four, the shared core by the three that were folded
+        reached = {"ts_core.h"} if binding is _cabi else {"ts_core.h", "ts_index.h", "ts_launch.h"}
+        assert {os.path.join(csrc, h) for h in reached} <= seen, (binding.__name__, sorted(seen))
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from tiler_slider_amd import _cabi
     monkeypatch.setattr(_cabi, "_lib", None)

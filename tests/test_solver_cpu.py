@@ -9,23 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported
 from conftest import GOLDEN_DIR, ROOT
-
-
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ts_[a-z0-9_]+)\s*\(", text)))
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
-    return sorted(l.split()[-1] for l in out.splitlines() if re.search(r" T ts_", l))
-
-
-def _dims(S, T, mc=0, n=8, Tt=None):
-    from tiler_slider_amd import _cabi
-    return _cabi.Dims(n, S, T, T if Tt is None else Tt, mc, 100, 0)
 
 
 def test_search_library_exports_what_its_header_declares_and_the_step_library_is_unchanged():
@@ -190,7 +175,7 @@ def test_wave_form_has_no_block_barrier():
     assert len(block) == 4 and all(block.values()), block
 
 
-def test_compile_guarded_tells_a_small_library_from_a_parse_failure():
+def test_compile_guarded_tells_a_small_library_from_a_parse_failure(monkeypatch):
     """compile_guarded's last check takes "no kernel fills its register allocation" for unparsed metadata - right for the step
     library's hundreds of kernels, wrong for a handful.  With min_kernels the check counts parsed kernels instead; the step
     library's call (min_kernels=None) is what it was."""
@@ -198,8 +183,9 @@ def test_compile_guarded_tells_a_small_library_from_a_parse_failure():
     from tiler_slider_amd import _cabi, _search_cabi
     sig = inspect.signature(_cabi.compile_guarded)
     assert sig.parameters["min_kernels"].default is None
-    assert "min_kernels" not in inspect.getsource(_cabi.build_library)
-    assert "min_kernels=MIN_KERNELS" in inspect.getsource(_search_cabi.build_library)
+    assert _cabi.MIN_KERNELS is None and _search_cabi.MIN_KERNELS == 12
+    _assert_build_goes_through_the_guard(_cabi, monkeypatch)
+    _assert_build_goes_through_the_guard(_search_cabi, monkeypatch)
 
 
 def test_yardstick_reproduces_the_recorded_optimum_of_the_400_screenshot_levels(oracle):

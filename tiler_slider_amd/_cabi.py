@@ -8,14 +8,18 @@ import ctypes as C
 import os
 import shutil
 import subprocess
+import sys
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_PKG)
 SRC = os.path.join(_PKG, "csrc", "ts_kernels.hip")
 HEADERS = [os.path.join(_PKG, "csrc", "ts_core.h"), os.path.join(ROOT, "include", "tiler_slider.h")]
 LIB_PATH = os.path.join(_PKG, "lib", "libtiler_slider_hip.so")
+# what ts_search.hip, ts_table.hip and ts_rollout.hip share beyond ts_core.h: the index space and the host side of a launch
+SHARED_HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("ts_index.h", "ts_launch.h")]
 
 ABI_VERSION = 6
+MIN_KERNELS = None  # hundreds of kernels: compile_guarded recognises a parse failure by "no kernel fills its allocation"
 OK, ERR_NULL, ERR_DIMS, ERR_LIMIT, ERR_HIP, ERR_ARG = 0, -1, -2, -3, -4, -5
 FLAG_IS_WON, FLAG_INVALID_MOVE, FLAG_SUCCESS, FLAG_TIMEOUT = 0x01, 0x02, 0x04, 0x08
 FLAG_STEPPED_DONE, FLAG_AUTORESET, FLAG_BAD_ACTION = 0x10, 0x20, 0x40
@@ -52,18 +56,22 @@ OUT_OBS, OUT_REWARD, OUT_ONEHOT, OUT_VALID, OUT_OBS_U8, OUT_VALID4, OUT_FLAGS = 
 KERNEL_NAMES = {0: "none", 1: "k_small", 2: "k_multi", 3: "k_deal", 4: "k_lines", 5: "k_state"}
 
 
-class LaunchDesc(C.Structure):
+class Desc(C.Structure):
+    """A ts_*_desc: what one call would launch, as_dict() for the describe_* functions."""
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["name"] = self.name.decode()
+        return d
+
+
+class LaunchDesc(Desc):
     """ts_launch_desc of include/tiler_slider.h: what one call of the hot path would launch."""
     _fields_ = [("kernel", C.c_int32), ("out_of_cache", C.c_int32), ("lanes_per_board", C.c_int32), ("boards_per_lane", C.c_int32),
                 ("boards_per_wave", C.c_int32), ("tiles_per_lane", C.c_int32), ("extras", C.c_int32), ("wide", C.c_int32),
                 ("cached_every", C.c_int32), ("emit_edges", C.c_int32), ("xcd_piece", C.c_int32), ("waves_per_block", C.c_int32),
                 ("blocks_per_cu", C.c_int32), ("lds_bytes_block", C.c_int32), ("lds_bytes_used", C.c_int32), ("reserved", C.c_int32),
                 ("blocks", C.c_int64), ("output_bytes", C.c_int64), ("resident_bytes", C.c_int64), ("name", C.c_char * 64)]
-
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
-        d["name"] = self.name.decode()
-        return d
 
 
 def describe_launch(dims, op=OP_STEP, outputs=OUT_OBS):
@@ -75,13 +83,6 @@ def describe_launch(dims, op=OP_STEP, outputs=OUT_OBS):
 
 class TilerSliderLibraryError(RuntimeError):
     pass
-
-
-def _stale():
-    if not os.path.exists(LIB_PATH):
-        return True
-    built = os.path.getmtime(LIB_PATH)
-    return any(os.path.getmtime(p) > built for p in [SRC] + HEADERS)
 
 
 _LLVM_BIN = "/opt/rocm/lib/llvm/bin"
@@ -181,40 +182,59 @@ def compile_guarded(src, out_lib, defines=(), work=None, verbose=False, keep_asm
     return report
 
 
-def build_library(force=False, verbose=False):
-    """Compile the HIP kernels for gfx950 in-tree (hipcc cross-compiles without a GPU), through compile_guarded."""
-    if not force and not _stale():
-        return LIB_PATH
-    compile_guarded(SRC, LIB_PATH, verbose=verbose, keep_asm=os.environ.get("TS_KEEP_ASM") == "1")
-    return LIB_PATH
+def bind(module, label, prefix, declare):
+    """(build_library, lib, check) of a binding module - this one or _search_cabi, _table_cabi, _rollout_cabi.  The module
+    keeps SRC, HEADERS, LIB_PATH, EXPORTS, ABI_VERSION, MIN_KERNELS and _lib as its own attributes, read when a function is
+    called; `label`: the library's name in the ABI-mismatch message; `prefix`: its <prefix>abi_version and
+    <prefix>last_hip_error symbols; declare(L): the prototypes of its entry points."""
+    m = sys.modules[module]
+
+    def build_library(force=False, verbose=False):
+        """Compile the library for gfx950 in-tree (hipcc cross-compiles without a GPU), through compile_guarded, if it is older
+        than its source or a header it includes."""
+        stale = not os.path.exists(m.LIB_PATH) or any(os.path.getmtime(p) > os.path.getmtime(m.LIB_PATH) for p in [m.SRC] + m.HEADERS)
+        if force or stale:
+            compile_guarded(m.SRC, m.LIB_PATH, verbose=verbose, keep_asm=os.environ.get("TS_KEEP_ASM") == "1", min_kernels=m.MIN_KERNELS)
+        return m.LIB_PATH
+
+    def lib():
+        """The loaded shared library; raises (never falls back) when it is unavailable."""
+        if m._lib is not None:
+            return m._lib
+        if not os.path.exists(m.LIB_PATH):
+            raise TilerSliderLibraryError(
+                f"{m.LIB_PATH} is missing: the HIP extension has not been built. Run "
+                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
+        try:
+            L = C.CDLL(m.LIB_PATH)
+        except OSError as e:
+            raise TilerSliderLibraryError(f"cannot load {m.LIB_PATH}: {e}") from e
+        missing = [s for s in m.EXPORTS if not hasattr(L, s)]
+        if missing:
+            raise TilerSliderLibraryError(f"{m.LIB_PATH} lacks symbols {missing}; rebuild it")
+        version, last_error = getattr(L, prefix + "abi_version"), getattr(L, prefix + "last_hip_error")
+        version.restype = last_error.restype = C.c_int32
+        declare(L)
+        if version() != m.ABI_VERSION:
+            raise TilerSliderLibraryError(f"{label}ABI version {version()} != {m.ABI_VERSION}; rebuild the library")
+        m._lib = L
+        return L
+
+    def check(rc, what):
+        if rc != OK:
+            msg = _status_string(rc)
+            extra = f" (hipError {getattr(lib(), prefix + 'last_hip_error')()})" if rc == ERR_HIP else ""
+            raise TilerSliderLibraryError(f"{what}: {msg}{extra}")
+
+    return build_library, lib, check
 
 
-_lib = None
-
-
-def lib():
-    """The loaded shared library; raises (never falls back) when it is unavailable."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise TilerSliderLibraryError(
-            f"{LIB_PATH} is missing: the HIP extension has not been built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
-    try:
-        L = C.CDLL(LIB_PATH)
-    except OSError as e:
-        raise TilerSliderLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS if not hasattr(L, s)]
-    if missing:
-        raise TilerSliderLibraryError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
+def _declare(L):
     P, DP, SP = C.c_void_p, C.POINTER(Dims), C.POINTER(State)
-    L.ts_abi_version.restype = C.c_int32
     L.ts_limits.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.ts_limits.restype = None
     L.ts_status_string.argtypes = [C.c_int32]
     L.ts_status_string.restype = C.c_char_p
-    L.ts_last_hip_error.restype = C.c_int32
     L.ts_blk_words.argtypes = [C.c_int32]
     L.ts_blk_words.restype = C.c_int32
     L.ts_cell_bytes.argtypes = [C.c_int32]
@@ -245,18 +265,15 @@ def lib():
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = C.c_int32
-    if L.ts_abi_version() != ABI_VERSION:
-        raise TilerSliderLibraryError(f"ABI version {L.ts_abi_version()} != {ABI_VERSION}; rebuild the library")
-    _lib = L
-    return L
 
 
-def check(rc, what):
-    if rc != OK:
-        L = lib()
-        msg = L.ts_status_string(rc).decode()
-        extra = f" (hipError {L.ts_last_hip_error()})" if rc == ERR_HIP else ""
-        raise TilerSliderLibraryError(f"{what}: {msg}{extra}")
+_lib = None
+build_library, lib, check = bind(__name__, "", "ts_", _declare)
+
+
+def _status_string(rc):
+    """The text of a status code: the codes of all four libraries are the step library's."""
+    return lib().ts_status_string(rc).decode()
 
 
 def limits():

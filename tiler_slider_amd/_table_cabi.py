@@ -9,10 +9,10 @@ import ctypes as C
 import os
 
 from . import _cabi
-from ._cabi import Dims, State, TilerSliderLibraryError
+from ._cabi import Desc, Dims, State
 
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_table.hip")
-HEADERS = _cabi.HEADERS + [os.path.join(_cabi.ROOT, "include", "tiler_slider_search.h"), os.path.join(_cabi.ROOT, "include", "tiler_slider_table.h")]
+HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_table.so")
 
 ABI_VERSION = 1
@@ -25,55 +25,15 @@ EXPORTS = ("ts_table_abi_version", "ts_table_last_hip_error", "ts_table_states",
            "ts_describe_table_build", "ts_table_tuning")
 
 
-class TableDesc(C.Structure):
+class TableDesc(Desc):
     """ts_table_desc of include/tiler_slider_table.h: what one ts_table_build would launch."""
     _fields_ = [("form", C.c_int32), ("lanes_per_board", C.c_int32), ("boards_per_block", C.c_int32), ("threads_per_block", C.c_int32),
                 ("bitmap_words", C.c_int32), ("lds_bytes_board", C.c_int32), ("lds_bytes_block", C.c_int32), ("lds_bytes_max", C.c_int32),
                 ("states", C.c_int64), ("blocks", C.c_int64), ("table_bytes", C.c_int64), ("name", C.c_char * 64)]
 
-    def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_}
-        d["name"] = self.name.decode()
-        return d
 
-
-def _stale():
-    if not os.path.exists(LIB_PATH):
-        return True
-    built = os.path.getmtime(LIB_PATH)
-    return any(os.path.getmtime(p) > built for p in [SRC] + HEADERS)
-
-
-def build_library(force=False, verbose=False):
-    """Compile the tables' kernels for gfx950 in-tree, through the same guarded steps as the other two libraries."""
-    if not force and not _stale():
-        return LIB_PATH
-    _cabi.compile_guarded(SRC, LIB_PATH, verbose=verbose, keep_asm=os.environ.get("TS_KEEP_ASM") == "1", min_kernels=MIN_KERNELS)
-    return LIB_PATH
-
-
-_lib = None
-
-
-def lib():
-    """The loaded table library; raises (never falls back) when it is unavailable."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise TilerSliderLibraryError(
-            f"{LIB_PATH} is missing: the HIP extension has not been built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). There is no CPU fallback.")
-    try:
-        L = C.CDLL(LIB_PATH)
-    except OSError as e:
-        raise TilerSliderLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    missing = [s for s in EXPORTS if not hasattr(L, s)]
-    if missing:
-        raise TilerSliderLibraryError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
+def _declare(L):
     P, DP, SP = C.c_void_p, C.POINTER(Dims), C.POINTER(State)
-    L.ts_table_abi_version.restype = C.c_int32
-    L.ts_table_last_hip_error.restype = C.c_int32
     L.ts_table_states.argtypes = [DP]
     L.ts_table_states.restype = C.c_int64
     L.ts_table_build.argtypes = [DP, SP, C.c_int32, P, P]
@@ -84,17 +44,10 @@ def lib():
     L.ts_describe_table_build.restype = C.c_int32
     L.ts_table_tuning.argtypes = [C.c_int32, C.c_int64]
     L.ts_table_tuning.restype = C.c_int64
-    if L.ts_table_abi_version() != ABI_VERSION:
-        raise TilerSliderLibraryError(f"table ABI version {L.ts_table_abi_version()} != {ABI_VERSION}; rebuild the library")
-    _lib = L
-    return L
 
 
-def check(rc, what):
-    if rc != _cabi.OK:
-        msg = _cabi.lib().ts_status_string(rc).decode()  # the status codes are the step library's
-        extra = f" (hipError {lib().ts_table_last_hip_error()})" if rc == _cabi.ERR_HIP else ""
-        raise TilerSliderLibraryError(f"{what}: {msg}{extra}")
+_lib = None
+build_library, lib, check = _cabi.bind(__name__, "table ", "ts_table_", _declare)
 
 
 def table_states(dims):

@@ -10,7 +10,7 @@
 //
 // The transition is ts::slide_cell<S> and the win test the bitboard comparison of ts_core.h - the arithmetic of the step
 // kernels -, the action stream is ts::mix64 with the constants of ts_fill_actions, and the expert move is the rule of
-// k_table_lookup restated over the same five bytes of the board's row.  What the kernel must compute is fixed by the loop over
+// k_table_lookup (ts_index.h: best_moves, lowest_move) over the same five bytes of the board's row.  What the kernel must compute is fixed by the loop over
 // ts_fill_actions / ts_table_lookup / ts_step in the header; tests hold it to that loop byte for byte.
 //
 // Latency: the step loop is wave-uniform, key_k is a scalar per step.  The GIVEN action byte of step
@@ -18,20 +18,14 @@
 // about to play - and issues the five table reads of a step together, unconditionally, so that a step costs ONE memory round
 // trip where k_table_lookup's own order (the successors only once the board's entry is known) would cost two; the first table
 // read of step k + 1 depends on the cells step k produced, and that round trip per step is the floor of the policy.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-
 #include "../../include/tiler_slider_rollout.h"
-#include "ts_core.h"
+#include "ts_launch.h"
 
 namespace {
 
-constexpr int kWave = 64;
+using ts::kWave;
 constexpr int kThreads = 256;  // four waves per block; waves never interact
 constexpr int kMaxTargets = TS_ROLLOUT_MAX_TILES;
-
-thread_local int32_t t_last_hip_error = 0;
 
 struct RArgs {
   uint8_t *pos;  // cell_t = uint8 (S <= 8)
@@ -49,19 +43,12 @@ struct RArgs {
   uint32_t states;
 };
 
-template <int C>
-constexpr uint32_t pow_c(int t) {
-  uint32_t m = 1;
-  for (int i = 0; i < t; ++i) m *= (uint32_t)C;
-  return m;
-}
-
 // tiles a lane keeps: 8, fewer where the board has fewer cells or the table's index space fewer tiles (C^T <= 65536, T <= C:
 // 9^5 is the longest tuple)
 template <int S, int POLICY>
 constexpr int max_tiles() {
   constexpr int C = S * S;
-  constexpr int cap = POLICY == TS_ROLLOUT_TABLE ? 5 : TS_ROLLOUT_MAX_TILES;
+  constexpr int cap = POLICY == TS_ROLLOUT_TABLE ? ts::kMaxTiles : TS_ROLLOUT_MAX_TILES;
   return C < cap ? C : cap;
 }
 
@@ -83,8 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_rollout(const RArgs a) {
   const bool mc = a.mc != 0, autoreset = a.autoreset != 0;
 
   // ---- the board, once ----
-  M blk = (M)a.blk[nl];
-  if constexpr (BB::wide) blk |= (M)a.blk[N + nl] << 32;
+  M blk = ts::load_obstacles<S>(a.blk, N, nl);
   blk &= kFull;
   // Loads go out UNCONDITIONALLY, all before the first one is consumed: rows past the tile (target) count read the last row,
   // results unused.  (With a predicate per row the compiler waited for every single load: 2 T + Tt dependent round trips.)
@@ -154,14 +140,9 @@ __global__ __launch_bounds__(kThreads) void k_rollout(const RArgs a) {
     const uint64_t key = ts::mix64(a.seed ^ ((uint64_t)(a.step_index + k) * ts::kBoardMul));  // uniform: a scalar per step
     return ts::mix64(key + draw);
   };
-  // the rule of k_table_lookup on the board's own entry d0 and the entries d[] of its four successors
+  // k_table_lookup's answer from the board's own entry d0 and the entries d[] of its four successors
   auto expert_of = [](uint32_t d0, const uint32_t (&d)[4]) -> uint32_t {
-    uint32_t best = 0;
-    if (d0 >= 1u && d0 <= (uint32_t)TS_TABLE_MAX_DEPTH) {
-#pragma unroll
-      for (int dir = 0; dir < 4; ++dir) best |= (d[dir] == d0 - 1u ? 1u : 0u) << dir;
-    }
-    return best ? (uint32_t)ts::lsb(best) : 255u;
+    return ts::lowest_move(d0 >= 1u && d0 <= (uint32_t)TS_TABLE_MAX_DEPTH ? ts::best_moves(d0, d) : 0u);
   };
   auto choose = [&](uint32_t e, uint64_t r) -> uint32_t {
     const bool explore = (r & 0xffffffffull) < a.threshold;
@@ -205,16 +186,16 @@ __global__ __launch_bounds__(kThreads) void k_rollout(const RArgs a) {
       uint32_t q4[4][MT], idx[4], idx0 = 0;
 #pragma unroll
       for (int t = 0; t < MT; ++t)
-        if (t < T) idx0 += pc[t] * pow_c<C>(t);
+        if (t < T) idx0 += pc[t] * ts::pow_c<C>(t);
 #pragma unroll
       for (int dir = 0; dir < 4; ++dir) {
-        idx[dir] = 0;
+        idx[dir] = 0;  // the successor index, in place (ts_index.h says why)
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
           q4[dir][t] = pc[t];
           if (t < T) {
             q4[dir][t] = (uint32_t)ts::slide_cell<S>((int)pc[t], occ, blk, dir);  // a cell < C whatever the board: inside the row
-            idx[dir] += q4[dir][t] * pow_c<C>(t);
+            idx[dir] += q4[dir][t] * ts::pow_c<C>(t);
           }
         }
       }
@@ -310,14 +291,14 @@ __global__ __launch_bounds__(kThreads) void k_rollout(const RArgs a) {
 #pragma unroll
           for (int t = 0; t < MT; ++t) {
             pc[t] = min(p[t], (uint32_t)(C - 1));
-            if (t < T) occ |= M(1) << pc[t], idx0 += pc[t] * pow_c<C>(t);
+            if (t < T) occ |= M(1) << pc[t], idx0 += pc[t] * ts::pow_c<C>(t);
           }
 #pragma unroll
           for (int dir = 0; dir < 4; ++dir) {
             uint32_t idx = 0;
 #pragma unroll
             for (int t = 0; t < MT; ++t)
-              if (t < T) idx += (uint32_t)ts::slide_cell<S>((int)pc[t], occ, blk, dir) * pow_c<C>(t);
+              if (t < T) idx += (uint32_t)ts::slide_cell<S>((int)pc[t], occ, blk, dir) * ts::pow_c<C>(t);
             d[dir] = row[idx];
           }
           e = expert_of(row[idx0], d);
@@ -353,47 +334,25 @@ __global__ __launch_bounds__(kThreads) void k_rollout(const RArgs a) {
 
 using Kernel = void (*)(const RArgs);
 
-template <int P, int... Ss>
-Kernel by_size(int S) {
-  Kernel k = nullptr;
-  (void)((S == Ss && (k = k_rollout<Ss, P>, true)) || ...);
-  return k;
+template <int P>
+Kernel policy_kernel(int S) {
+  return ts::by_size<Kernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> Kernel { return k_rollout<s, P>; });
 }
 Kernel kernel_of(int S, int policy) {
   switch (policy) {
-    case TS_ROLLOUT_GIVEN: return by_size<TS_ROLLOUT_GIVEN, 1, 2, 3, 4, 5, 6, 7, 8>(S);
-    case TS_ROLLOUT_RANDOM: return by_size<TS_ROLLOUT_RANDOM, 1, 2, 3, 4, 5, 6, 7, 8>(S);
-    case TS_ROLLOUT_TABLE: return by_size<TS_ROLLOUT_TABLE, 1, 2, 3, 4, 5, 6, 7, 8>(S);
+    case TS_ROLLOUT_GIVEN: return policy_kernel<TS_ROLLOUT_GIVEN>(S);
+    case TS_ROLLOUT_RANDOM: return policy_kernel<TS_ROLLOUT_RANDOM>(S);
+    case TS_ROLLOUT_TABLE: return policy_kernel<TS_ROLLOUT_TABLE>(S);
   }
   return nullptr;
 }
 
-int32_t check_dims(const ts_dims *d) {  // the checks of the table library
-  if (!d) return TS_ERR_NULL;
-  if (d->n_boards < 0 || d->size < 1 || d->n_tiles < 0 || d->n_targets < 0 || (d->multi_color != 0 && d->multi_color != 1)) return TS_ERR_DIMS;
-  if (d->size > TS_MAX_SIZE || d->n_tiles > TS_MAX_TILES || d->n_targets > TS_MAX_TILES) return TS_ERR_LIMIT;
-  if (d->n_tiles > d->size * d->size) return TS_ERR_DIMS;
-  return TS_OK;
-}
-
 bool valid_policy(int32_t p) { return p == TS_ROLLOUT_GIVEN || p == TS_ROLLOUT_RANDOM || p == TS_ROLLOUT_TABLE; }
-
-// (S*S)^T where the tables hold it (<= TS_SOLVE_MAX_STATES), else 0: ts_table_states' rule, restated (a CPU test holds the
-// two together)
-int64_t table_states(const ts_dims *d) {
-  const int64_t C = (int64_t)d->size * d->size;
-  int64_t states = 1;
-  for (int t = 0; t < d->n_tiles; ++t) {
-    states *= C;
-    if (states > TS_SOLVE_MAX_STATES) return 0;
-  }
-  return states;
-}
 
 // valid dims: does a board fit a lane's registers (and, for TABLE, the tables)?  An unknown policy has no table rule.
 bool shape_supported(const ts_dims *d, int32_t policy) {
   if (d->size > TS_ROLLOUT_MAX_SIZE || d->n_tiles > TS_ROLLOUT_MAX_TILES || d->n_targets > TS_ROLLOUT_MAX_TILES) return false;
-  return policy != TS_ROLLOUT_TABLE || table_states(d) > 0;
+  return policy != TS_ROLLOUT_TABLE || ts::index_states(d) > 0;  // ts_table_states' rule
 }
 
 struct Plan {
@@ -404,7 +363,7 @@ struct Plan {
 
 // Every check of ts_rollout that needs no pointer of st / out, and the launch it would make; touches no device.
 int32_t plan_rollout(const ts_dims *d, const ts_rollout_cfg *cfg, uint32_t out_mask, Plan &p) {
-  if (const int32_t rc = check_dims(d); rc != TS_OK) return rc;
+  if (const int32_t rc = ts::check_dims(d); rc != TS_OK) return rc;
   if (!cfg) return TS_ERR_NULL;
   if (!shape_supported(d, cfg->policy)) return TS_ERR_LIMIT;
   if ((cfg->mode & ~TS_MODE_AUTORESET) || !valid_policy(cfg->policy) || cfg->steps < 0 || cfg->steps > TS_ROLLOUT_MAX_STEPS ||
@@ -430,10 +389,10 @@ int32_t plan_rollout(const ts_dims *d, const ts_rollout_cfg *cfg, uint32_t out_m
 extern "C" {
 
 int32_t ts_rollout_abi_version(void) { return TS_ROLLOUT_ABI_VERSION; }
-int32_t ts_rollout_last_hip_error(void) { return t_last_hip_error; }
+int32_t ts_rollout_last_hip_error(void) { return ts::t_last_hip_error; }
 
 int32_t ts_rollout_supported(const ts_dims *dims, int32_t policy) {
-  const int32_t rc = check_dims(dims);
+  const int32_t rc = ts::check_dims(dims);
   if (rc == TS_ERR_LIMIT) return 0;
   if (rc != TS_OK) return rc;
   if (!valid_policy(policy)) return TS_ERR_ARG;
@@ -475,14 +434,9 @@ int32_t ts_rollout(const ts_dims *dims, const ts_state *st, const ts_rollout_cfg
   a.seed = cfg->seed, a.threshold = cfg->explore_threshold;
   a.T = dims->n_tiles, a.Tt = dims->n_targets, a.mc = dims->multi_color, a.max_steps = dims->max_steps, a.steps = cfg->steps;
   a.autoreset = autoreset ? 1 : 0, a.write_state = cfg->write_state ? 1 : 0;
-  a.states = cfg->policy == TS_ROLLOUT_TABLE ? (uint32_t)table_states(dims) : 0u;
+  a.states = cfg->policy == TS_ROLLOUT_TABLE ? (uint32_t)ts::index_states(dims) : 0u;
   hipLaunchKernelGGL(p.kernel, dim3(p.blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    t_last_hip_error = (int32_t)e;
-    return TS_ERR_HIP;
-  }
-  return TS_OK;
+  return ts::finish_launch();
 }
 
 }  // extern "C"

@@ -26,23 +26,17 @@
 //                     wave-uniform: groups whose board is finished idle until the wave's last board is.
 //   k_solve_block<S>  one board per block of four waves, for index spaces of thousands of words.
 // The boundary between them is policy::kWaveMaxStates below.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdio>
-
-#include "../../include/tiler_slider_search.h"
-#include "ts_core.h"
+//
+// Shared with ts_table.hip and ts_rollout.hip: the index space (ts_index.h) and the host side of a launch - the checks, the
+// wave-or-block plan, the error tail, the knobs (ts_launch.h).  What was measured for THIS library stays here.
+#include "ts_launch.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kBlockThreads = 256;  // k_solve_block: four waves
-constexpr int kMaxTiles = 5;        // C^T <= 65536 with T <= C: 9^5 = 59,049 is the longest tuple (3x3)
+using ts::kBlockThreads, ts::kMaxTiles, ts::kWave;
+// LDS of a board (ts::kMaxBlockLds bounds a block's): the largest request is one board of 65,536 states, 7 * 8 KiB + 12 B
 constexpr int kBitmaps = 7, kCtlWords = 3;
-// Dynamic LDS a block may ask for: the bound the step library allows itself (ts_kernels.hip: kMaxBlockLds).  The largest
-// request here is one board of 65,536 states: 7 * 8 KiB + 12 B.
-constexpr size_t kMaxBlockLds = 64 * 1024;
+static_assert(TS_SOLVE_FORM_NONE == ts::kFormNone && TS_SOLVE_FORM_WAVE == ts::kFormWave && TS_SOLVE_FORM_BLOCK == ts::kFormBlock);
 
 namespace policy {
 // Index spaces up to this size take the wave form (ts_search_tuning(TS_SOLVE_TUNE_WAVE_MAX_STATES)).  Measured, MI355X, us per
@@ -62,7 +56,6 @@ constexpr int64_t kWaveMaxStates = 8192;
 constexpr int64_t kWordsPerLane = 1;
 }  // namespace policy
 
-thread_local int32_t t_last_hip_error = 0;
 std::atomic<int64_t> g_wave_max_states{policy::kWaveMaxStates};
 std::atomic<int64_t> g_words_per_lane{policy::kWordsPerLane};
 
@@ -85,12 +78,7 @@ __device__ __forceinline__ void solve_body(const SArgs &a) {
   constexpr uint32_t C = BB::C;
   extern __shared__ uint32_t lds[];
 
-  const uint32_t G = BLOCK ? (uint32_t)kBlockThreads : (1u << a.lanes_log2);  // threads per board
-  const uint32_t g = threadIdx.x & (G - 1u);
-  const uint32_t grp = BLOCK ? 0u : threadIdx.x >> a.lanes_log2;
-  const int64_t n = BLOCK ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * (int64_t)(kWave >> a.lanes_log2) + grp;
-  const bool live = n < a.N;
-  const int64_t nl = live ? n : a.N - 1;  // idle groups read the last board (N >= 1) and write nothing
+  const auto [G, g, grp, n, nl, live] = ts::group_of<BLOCK>(threadIdx.x, blockIdx.x, a.lanes_log2, a.N);
   const int64_t N = a.N;
   const int T = a.T, Tt = a.Tt;
   const uint32_t W = a.words;
@@ -100,8 +88,8 @@ __device__ __forceinline__ void solve_body(const SArgs &a) {
   for (uint32_t i = g; i < a.board_words; i += G) base[i] = 0;
 
   // the level and the root (cell ids clamped as the step kernels clamp them)
-  M blk = (M)a.blk[nl];
-  if constexpr (BB::wide) blk |= (M)a.blk[N + nl] << 32;
+  M blk = ts::load_obstacles<S>(a.blk, N, nl);
+  // root encode, win test and decode stay in place here: as ts_index.h's functions they changed all 12 search kernels (ts_index.h)
   uint32_t root = 0;
   M occ_root = 0;
   {
@@ -171,7 +159,7 @@ __device__ __forceinline__ void solve_body(const SArgs &a) {
           bits &= bits - 1u;
           const uint32_t s = w * 32u + b;
           uint32_t p[kMaxTiles];
-          M occ = 0;
+          M occ = 0;  // decode, in place (see the root)
           {
             uint32_t r = s;
 #pragma unroll
@@ -191,7 +179,7 @@ __device__ __forceinline__ void solve_body(const SArgs &a) {
           }
 #pragma unroll
           for (int dir = 0; dir < 4; ++dir) {
-            uint32_t idx = 0, mul = 1;
+            uint32_t idx = 0, mul = 1;  // the successor index, in place (ts_index.h says why)
             M occ2 = 0;
 #pragma unroll
             for (int t = 0; t < kMaxTiles; ++t) {
@@ -258,88 +246,32 @@ __global__ __launch_bounds__(kBlockThreads) void k_solve_block(const SArgs a) {
 
 using SolveKernel = void (*)(const SArgs);
 
-template <int... Vs, class F>
-SolveKernel by_size(int v, F f) {
-  SolveKernel k = nullptr;
-  (void)((v == Vs && (k = f(std::integral_constant<int, Vs>{}), true)) || ...);
-  return k;
-}
 SolveKernel wave_kernel(int S) {
-  return by_size<1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> SolveKernel { return k_solve_wave<s>; });
+  return ts::by_size<SolveKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> SolveKernel { return k_solve_wave<s>; });
 }
 // the block form is compiled where an index space above policy::kWaveMaxStates exists: 9^5, 16^4, 25^3, 36^3 (49^2 and 64^2 stay below)
 SolveKernel block_kernel(int S) {
-  return by_size<3, 4, 5, 6>(S, [](auto s) -> SolveKernel { return k_solve_block<s>; });
-}
-
-int32_t check_dims(const ts_dims *d) {
-  if (!d) return TS_ERR_NULL;
-  if (d->n_boards < 0 || d->size < 1 || d->n_tiles < 0 || d->n_targets < 0 || (d->multi_color != 0 && d->multi_color != 1)) return TS_ERR_DIMS;
-  if (d->size > TS_MAX_SIZE || d->n_tiles > TS_MAX_TILES || d->n_targets > TS_MAX_TILES) return TS_ERR_LIMIT;
-  if (d->n_tiles > d->size * d->size) return TS_ERR_DIMS;
-  return TS_OK;
-}
-
-int64_t solve_states(const ts_dims *d) {
-  if (const int32_t rc = check_dims(d); rc != TS_OK) return rc;
-  if (d->size > TS_SOLVE_MAX_SIZE) return 0;
-  const int64_t C = (int64_t)d->size * d->size;
-  int64_t states = 1;
-  for (int t = 0; t < d->n_tiles; ++t) {
-    states *= C;
-    if (states > TS_SOLVE_MAX_STATES) return 0;
-  }
-  return states;
+  return ts::by_size<SolveKernel, 3, 4, 5, 6>(S, [](auto s) -> SolveKernel { return k_solve_block<s>; });
 }
 
 struct SolvePlan {
-  SolveKernel kernel = nullptr;
+  ts::FormPlan<SolveKernel> f;
   SArgs a{};
-  uint32_t blocks = 0, threads = 0;
-  size_t lds = 0;
   ts_solve_desc desc{};
 };
 
 // Everything ts_solve decides before it launches; touches no device (ts_describe_solve reports it).
 int32_t plan_solve(const ts_dims *d, SolvePlan &p) {
-  const int64_t states = solve_states(d);
-  if (states < 0) return (int32_t)states;
-  if (states == 0) return TS_ERR_LIMIT;
-  const int S = d->size;
+  const auto choose = [&](int64_t states, uint32_t words) -> ts::FormChoice<SolveKernel> {
+    const int64_t wpl = std::max<int64_t>(g_words_per_lane.load(std::memory_order_relaxed), 1);
+    return {states > g_wave_max_states.load(std::memory_order_relaxed) ? block_kernel(d->size) : nullptr, wave_kernel(d->size),
+            ((int64_t)words + wpl - 1) / wpl};
+  };
+  if (const int32_t rc = ts::plan_forms(d, kBitmaps, kCtlWords, "k_solve", choose, p.f); rc != TS_OK) return rc;
   SArgs &a = p.a;
   a.N = d->n_boards, a.T = d->n_tiles, a.Tt = d->n_targets, a.mc = d->multi_color;
-  a.words = (uint32_t)((states + 31) / 32);
-  a.board_words = kBitmaps * a.words + kCtlWords;
-  p.desc.states = states;
-  p.desc.bitmap_words = (int32_t)a.words;
-  p.desc.lds_bytes_board = (int32_t)(a.board_words * 4u);
-  if (d->n_boards == 0) return TS_OK;  // TS_SOLVE_FORM_NONE
-  SolveKernel blockk = states > g_wave_max_states.load(std::memory_order_relaxed) ? block_kernel(S) : nullptr;
-  int64_t blocks;
-  if (blockk) {
-    p.kernel = blockk;
-    p.threads = kBlockThreads;
-    p.desc.form = TS_SOLVE_FORM_BLOCK, p.desc.lanes_per_board = kBlockThreads, p.desc.boards_per_block = 1;
-    blocks = d->n_boards;
-    snprintf(p.desc.name, sizeof p.desc.name, "k_solve_block<%d>", S);
-  } else {
-    p.kernel = wave_kernel(S);
-    int64_t wpl = g_words_per_lane.load(std::memory_order_relaxed);
-    if (wpl < 1) wpl = 1;
-    const int64_t want = ((int64_t)a.words + wpl - 1) / wpl;
-    while ((1 << a.lanes_log2) < kWave && (1 << a.lanes_log2) < want) ++a.lanes_log2;
-    const int lanes = 1 << a.lanes_log2, bpb = kWave / lanes;
-    p.threads = kWave;
-    p.desc.form = TS_SOLVE_FORM_WAVE, p.desc.lanes_per_board = lanes, p.desc.boards_per_block = bpb;
-    blocks = (d->n_boards + bpb - 1) / bpb;
-    snprintf(p.desc.name, sizeof p.desc.name, "k_solve_wave<%d>", S);
-  }
-  p.lds = (size_t)p.desc.boards_per_block * a.board_words * 4u;
-  if (!p.kernel || p.lds > kMaxBlockLds || blocks > 0x7fffffffll) return TS_ERR_LIMIT;
-  p.blocks = (uint32_t)blocks;
-  p.desc.threads_per_block = (int32_t)p.threads;
-  p.desc.lds_bytes_block = (int32_t)p.lds;
-  p.desc.blocks = blocks;
+  a.words = p.f.words, a.board_words = p.f.board_words, a.lanes_log2 = p.f.lanes_log2;
+  ts::describe_forms(p.f, p.desc);
   return TS_OK;
 }
 
@@ -348,9 +280,9 @@ int32_t plan_solve(const ts_dims *d, SolvePlan &p) {
 extern "C" {
 
 int32_t ts_search_abi_version(void) { return TS_SEARCH_ABI_VERSION; }
-int32_t ts_search_last_hip_error(void) { return t_last_hip_error; }
+int32_t ts_search_last_hip_error(void) { return ts::t_last_hip_error; }
 
-int64_t ts_solve_states(const ts_dims *dims) { return solve_states(dims); }
+int64_t ts_solve_states(const ts_dims *dims) { return ts::checked_states(dims); }
 
 int32_t ts_describe_solve(const ts_dims *dims, ts_solve_desc *desc) {
   if (!dims || !desc) return TS_ERR_NULL;
@@ -370,19 +302,13 @@ int32_t ts_solve(const ts_dims *dims, const ts_state *st, int32_t max_depth, int
   if (!st || !moves || !st->blk || (dims->n_tiles > 0 && !st->pos) || (dims->n_targets > 0 && !st->tgt)) return TS_ERR_NULL;
   p.a.pos = static_cast<const uint8_t *>(st->pos), p.a.tgt = static_cast<const uint8_t *>(st->tgt), p.a.blk = st->blk;
   p.a.moves = moves, p.a.best = best, p.a.max_depth = max_depth;
-  hipLaunchKernelGGL(p.kernel, dim3(p.blocks), dim3(p.threads), p.lds, static_cast<hipStream_t>(stream), p.a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    t_last_hip_error = (int32_t)e;
-    return TS_ERR_HIP;
-  }
-  return TS_OK;
+  hipLaunchKernelGGL(p.f.kernel, dim3(p.f.blocks), dim3(p.f.threads), p.f.lds, static_cast<hipStream_t>(stream), p.a);
+  return ts::finish_launch();
 }
 
 int64_t ts_search_tuning(int32_t key, int64_t value) {
   std::atomic<int64_t> *knob = key == TS_SOLVE_TUNE_WAVE_MAX_STATES ? &g_wave_max_states : key == TS_SOLVE_TUNE_WORDS_PER_LANE ? &g_words_per_lane : nullptr;
-  if (!knob) return -1;
-  return value >= 0 ? knob->exchange(value, std::memory_order_relaxed) : knob->load(std::memory_order_relaxed);
+  return ts::tune(knob, value);
 }
 
 }  // extern "C"

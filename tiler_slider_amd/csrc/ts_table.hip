@@ -21,23 +21,19 @@
 //   k_table_wave<S>   blocks of ONE wave (no s_barrier); a board is worked by G = 1 .. 64 lanes, 64 / G boards per wave
 //   k_table_block<S>  one board per block of four waves
 // and the lookup, k_table_lookup<S>: one board per lane, no LDS, five byte reads.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdio>
-
+//
+// The index space, the win test and the expert rule are the solver's and the rollouts' too (ts_index.h), and so is the host side
+// of a launch (ts_launch.h); the measured policy of THIS library stays here.
 #include "../../include/tiler_slider_table.h"
-#include "ts_core.h"
+#include "ts_launch.h"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kBlockThreads = 256;  // k_table_block and k_table_lookup: four waves
-constexpr int kMaxTiles = 5;        // C^T <= 65536 with T <= C: 9^5 = 59,049 is the longest tuple (3x3)
+using ts::kBlockThreads, ts::kMaxTiles, ts::kWave;  // kBlockThreads: k_table_block and k_table_lookup
+// LDS of a board (ts::kMaxBlockLds bounds a block's): the largest request is one board of 65,536 states, 3 * 8 KiB + 8 B, so the
+// default limit of a block is kept on purpose (bitmaps, not bytes, in LDS).
 constexpr int kBitmaps = 3, kCtlWords = 2;
-// Dynamic LDS a block may ask for.  The largest request here is one board of 65,536 states: 3 * 8 KiB + 8 B, so the
-// default limit of a block is kept on purpose (bitmaps, not bytes, in LDS) and hipFuncSetAttribute is never needed.
-constexpr size_t kMaxBlockLds = 64 * 1024;
+static_assert(TS_TABLE_FORM_NONE == ts::kFormNone && TS_TABLE_FORM_WAVE == ts::kFormWave && TS_TABLE_FORM_BLOCK == ts::kFormBlock);
 
 namespace policy {
 // Measured, MI355X, us per launch of ts_table_build on random levels, wave form (64 lanes per board) / block form
@@ -65,7 +61,6 @@ constexpr int64_t kBlockBelowBoards = 32768;
 constexpr int64_t kStatesPerLane = 1;
 }  // namespace policy
 
-thread_local int32_t t_last_hip_error = 0;
 std::atomic<int64_t> g_wave_max_states{policy::kWaveMaxStates};
 std::atomic<int64_t> g_states_per_lane{policy::kStatesPerLane};
 std::atomic<int64_t> g_block_below_boards{policy::kBlockBelowBoards};
@@ -89,12 +84,7 @@ __device__ __forceinline__ void table_body(const BArgs &a) {
   constexpr uint32_t C = BB::C;
   extern __shared__ uint32_t lds[];
 
-  const uint32_t G = BLOCK ? (uint32_t)kBlockThreads : (1u << a.lanes_log2);  // threads per board
-  const uint32_t g = threadIdx.x & (G - 1u);
-  const uint32_t grp = BLOCK ? 0u : threadIdx.x >> a.lanes_log2;
-  const int64_t n = BLOCK ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * (int64_t)(kWave >> a.lanes_log2) + grp;
-  const bool live = n < a.N;
-  const int64_t nl = live ? n : a.N - 1;  // idle groups read the last board (N >= 1) and write nothing
+  const auto [G, g, grp, n, nl, live] = ts::group_of<BLOCK>(threadIdx.x, blockIdx.x, a.lanes_log2, a.N);
   const int64_t N = a.N;
   const int T = a.T, Tt = a.Tt;
   const uint32_t W = a.words, states = a.states;
@@ -103,43 +93,10 @@ __device__ __forceinline__ void table_body(const BArgs &a) {
   uint32_t *closed = base, *prev = base + W, *cur = base + 2 * W, *ctl = base + kBitmaps * W;
   for (uint32_t i = g; i < a.board_words; i += G) base[i] = 0;
 
-  // the level (cell ids clamped as the step kernels clamp them)
-  M blk = (M)a.blk[nl];
-  if constexpr (BB::wide) blk |= (M)a.blk[N + nl] << 32;
-  // win test (state.py:172-186), the two comparisons of the solver: multi-colour: the state IS the targets' index (and
-  // T == Tt); single colour: the set of tile cells equals the set of target cells
-  M tgm = 0;
-  uint32_t tgt_idx = 0;
-  {
-    uint32_t mul = 1;
-    for (int j = 0; j < Tt; ++j) {
-      const uint32_t tj = min((uint32_t)a.tgt[(int64_t)j * N + nl], C - 1u);
-      tgm |= M(1) << tj;
-      if (j < T) {
-        tgt_idx += tj * mul;
-        mul *= C;
-      }
-    }
-  }
-  const bool mc = a.mc != 0, mc_can_win = T == Tt;
+  // the level (cell ids clamped as the step kernels clamp them) and the solver's win test
+  M blk = ts::load_obstacles<S>(a.blk, N, nl);
+  const ts::WinTest<S> is_won = ts::load_win_test<S>(a.tgt, N, nl, T, Tt, a.mc != 0);
   uint8_t *row = a.table + nl * (int64_t)states;  // written only where `live`
-
-  auto decode = [&](uint32_t s, uint32_t (&p)[kMaxTiles], M &occ, bool &valid) {
-    uint32_t r = s;
-    occ = 0;
-    valid = true;
-#pragma unroll
-    for (int t = 0; t < kMaxTiles; ++t) {
-      p[t] = 0;
-      if (t < T) {
-        p[t] = r % C;
-        r /= C;
-        const M bit = M(1) << p[t];
-        valid = valid && !((occ | blk) & bit);
-        occ |= bit;
-      }
-    }
-  };
 
   __syncthreads();
   // round 0: invalid placements and won ones; the bits of one word come from several lanes (ds_or)
@@ -147,9 +104,8 @@ __device__ __forceinline__ void table_body(const BArgs &a) {
     for (uint32_t s = g; s < states; s += G) {
       uint32_t p[kMaxTiles];
       M occ;
-      bool valid;
-      decode(s, p, occ, valid);
-      const bool won = valid && (mc ? (mc_can_win && s == tgt_idx) : occ == tgm);
+      const bool valid = ts::decode_cells<S>(s, T, blk, p, occ);
+      const bool won = valid && is_won(s, occ);
       const uint32_t w = s >> 5, bit = 1u << (s & 31);
       if (!valid || won) {
         atomicOr(&closed[w], bit);
@@ -188,12 +144,11 @@ __device__ __forceinline__ void table_body(const BArgs &a) {
         if (closed[w] & bit) continue;
         uint32_t p[kMaxTiles];
         M occ;
-        bool valid;
-        decode(s, p, occ, valid);  // valid: every invalid placement is closed
+        ts::decode_cells<S>(s, T, blk, p, occ);  // a placement: every invalid one is closed
         bool hit = false;
 #pragma unroll
         for (int dir = 0; dir < 4; ++dir) {
-          uint32_t idx = 0, mul = 1;
+          uint32_t idx = 0, mul = 1;  // the successor index, in place (ts_index.h says why)
 #pragma unroll
           for (int t = 0; t < kMaxTiles; ++t) {
             if (t < T) {
@@ -263,30 +218,17 @@ __global__ __launch_bounds__(kBlockThreads) void k_table_lookup(const LArgs a) {
   uint32_t best = 0;
   if (r >= 0 && r < a.n_rows) {
     const uint8_t *row = a.table + r * (int64_t)a.states;
-    M blk = (M)a.blk[n];
-    if constexpr (BB::wide) blk |= (M)a.blk[N + n] << 32;
-    uint32_t p[kMaxTiles], idx0 = 0;
-    M occ = 0;
-    {
-      uint32_t mul = 1;
-#pragma unroll
-      for (int t = 0; t < kMaxTiles; ++t) {
-        p[t] = 0;
-        if (t < T) {
-          p[t] = min((uint32_t)a.pos[(int64_t)t * N + n], C - 1u);  // idx0 <= C^T - 1: inside the row
-          idx0 += p[t] * mul;
-          mul *= C;
-          occ |= M(1) << p[t];
-        }
-      }
-    }
-    const uint32_t d0 = row[idx0];
+    M blk = ts::load_obstacles<S>(a.blk, N, n);
+    uint32_t p[kMaxTiles];
+    M occ;
+    const uint32_t d0 = row[ts::encode_cells<S>(a.pos, N, n, T, p, occ)];  // both indices read here stay inside the row
     if (d0 <= (uint32_t)TS_TABLE_MAX_DEPTH) {
       moves = (int32_t)d0;
       if (d0 >= 1u && (a.best || a.action)) {
+        uint32_t d[4];
 #pragma unroll
         for (int dir = 0; dir < 4; ++dir) {
-          uint32_t idx = 0, mul = 1;
+          uint32_t idx = 0, mul = 1;  // the successor index, in place (ts_index.h says why)
 #pragma unroll
           for (int t = 0; t < kMaxTiles; ++t) {
             if (t < T) {
@@ -294,8 +236,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_table_lookup(const LArgs a) {
               mul *= C;
             }
           }
-          best |= ((uint32_t)row[idx] == d0 - 1u ? 1u : 0u) << dir;
+          d[dir] = row[idx];
         }
+        best = ts::best_moves(d0, d);
       }
     } else if (d0 == (uint32_t)TS_TABLE_DEEP) {
       moves = TS_SOLVE_DEPTH;
@@ -303,113 +246,46 @@ __global__ __launch_bounds__(kBlockThreads) void k_table_lookup(const LArgs a) {
   }
   if (a.moves) a.moves[n] = (int16_t)moves;
   if (a.best) a.best[n] = (uint8_t)best;
-  if (a.action) a.action[n] = best ? (uint8_t)ts::lsb(best) : (uint8_t)255;
+  if (a.action) a.action[n] = (uint8_t)ts::lowest_move(best);
 }
 
 using BuildKernel = void (*)(const BArgs);
 using LookupKernel = void (*)(const LArgs);
 
-template <class K, int... Vs, class F>
-K by_size(int v, F f) {
-  K k = nullptr;
-  (void)((v == Vs && (k = f(std::integral_constant<int, Vs>{}), true)) || ...);
-  return k;
-}
 BuildKernel wave_kernel(int S) {
-  return by_size<BuildKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> BuildKernel { return k_table_wave<s>; });
+  return ts::by_size<BuildKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> BuildKernel { return k_table_wave<s>; });
 }
 // the block form is compiled where an index space of at least kBlockThreads placements exists: every size but 1x1
 BuildKernel block_kernel(int S) {
-  return by_size<BuildKernel, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> BuildKernel { return k_table_block<s>; });
+  return ts::by_size<BuildKernel, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> BuildKernel { return k_table_block<s>; });
 }
 LookupKernel lookup_kernel(int S) {
-  return by_size<LookupKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> LookupKernel { return k_table_lookup<s>; });
-}
-
-int32_t check_dims(const ts_dims *d) {
-  if (!d) return TS_ERR_NULL;
-  if (d->n_boards < 0 || d->size < 1 || d->n_tiles < 0 || d->n_targets < 0 || (d->multi_color != 0 && d->multi_color != 1)) return TS_ERR_DIMS;
-  if (d->size > TS_MAX_SIZE || d->n_tiles > TS_MAX_TILES || d->n_targets > TS_MAX_TILES) return TS_ERR_LIMIT;
-  if (d->n_tiles > d->size * d->size) return TS_ERR_DIMS;
-  return TS_OK;
-}
-
-int64_t table_states(const ts_dims *d) {
-  if (const int32_t rc = check_dims(d); rc != TS_OK) return rc;
-  if (d->size > TS_SOLVE_MAX_SIZE) return 0;
-  const int64_t C = (int64_t)d->size * d->size;
-  int64_t states = 1;
-  for (int t = 0; t < d->n_tiles; ++t) {
-    states *= C;
-    if (states > TS_SOLVE_MAX_STATES) return 0;
-  }
-  return states;
+  return ts::by_size<LookupKernel, 1, 2, 3, 4, 5, 6, 7, 8>(S, [](auto s) -> LookupKernel { return k_table_lookup<s>; });
 }
 
 struct BuildPlan {
-  BuildKernel kernel = nullptr;
+  ts::FormPlan<BuildKernel> f;
   BArgs a{};
-  uint32_t blocks = 0, threads = 0;
-  size_t lds = 0;
   ts_table_desc desc{};
 };
 
 // Everything ts_table_build decides before it launches; touches no device (ts_describe_table_build reports it).
 int32_t plan_build(const ts_dims *d, BuildPlan &p) {
-  const int64_t states = table_states(d);
-  if (states < 0) return (int32_t)states;
-  if (states == 0) return TS_ERR_LIMIT;
-  const int S = d->size;
-  BArgs &a = p.a;
-  a.N = d->n_boards, a.T = d->n_tiles, a.Tt = d->n_targets, a.mc = d->multi_color;
-  a.states = (uint32_t)states;
-  a.words = (uint32_t)((states + 31) / 32);
-  a.board_words = kBitmaps * a.words + kCtlWords;
-  p.desc.states = states;
-  p.desc.bitmap_words = (int32_t)a.words;
-  p.desc.lds_bytes_board = (int32_t)(a.board_words * 4u);
-  p.desc.lds_bytes_max = (int32_t)kMaxBlockLds;
-  p.desc.table_bytes = d->n_boards * states;
-  if (d->n_boards == 0) return TS_OK;  // TS_TABLE_FORM_NONE
   // a block per board for large index spaces, and for batches too small to fill the GPU with one wave per board - where the
   // block has a placement for every thread
-  const bool large = states > g_wave_max_states.load(std::memory_order_relaxed);
-  const bool few = states >= kBlockThreads && d->n_boards < g_block_below_boards.load(std::memory_order_relaxed);
-  BuildKernel blockk = large || few ? block_kernel(S) : nullptr;
-  int64_t blocks;
-  if (blockk) {
-    p.kernel = blockk;
-    p.threads = kBlockThreads;
-    p.desc.form = TS_TABLE_FORM_BLOCK, p.desc.lanes_per_board = kBlockThreads, p.desc.boards_per_block = 1;
-    blocks = d->n_boards;
-    snprintf(p.desc.name, sizeof p.desc.name, "k_table_block<%d>", S);
-  } else {
-    p.kernel = wave_kernel(S);
-    int64_t spl = g_states_per_lane.load(std::memory_order_relaxed);
-    if (spl < 1) spl = 1;
-    const int64_t want = (states + spl - 1) / spl;
-    while ((1 << a.lanes_log2) < kWave && (1 << a.lanes_log2) < want) ++a.lanes_log2;
-    const int lanes = 1 << a.lanes_log2, bpb = kWave / lanes;
-    p.threads = kWave;
-    p.desc.form = TS_TABLE_FORM_WAVE, p.desc.lanes_per_board = lanes, p.desc.boards_per_block = bpb;
-    blocks = (d->n_boards + bpb - 1) / bpb;
-    snprintf(p.desc.name, sizeof p.desc.name, "k_table_wave<%d>", S);
-  }
-  p.lds = (size_t)p.desc.boards_per_block * a.board_words * 4u;
-  if (!p.kernel || p.lds > kMaxBlockLds || blocks > 0x7fffffffll) return TS_ERR_LIMIT;
-  p.blocks = (uint32_t)blocks;
-  p.desc.threads_per_block = (int32_t)p.threads;
-  p.desc.lds_bytes_block = (int32_t)p.lds;
-  p.desc.blocks = blocks;
-  return TS_OK;
-}
-
-int32_t finish_launch() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    t_last_hip_error = (int32_t)e;
-    return TS_ERR_HIP;
-  }
+  const auto choose = [&](int64_t states, uint32_t) -> ts::FormChoice<BuildKernel> {
+    const bool large = states > g_wave_max_states.load(std::memory_order_relaxed);
+    const bool few = states >= kBlockThreads && d->n_boards < g_block_below_boards.load(std::memory_order_relaxed);
+    const int64_t spl = std::max<int64_t>(g_states_per_lane.load(std::memory_order_relaxed), 1);
+    return {large || few ? block_kernel(d->size) : nullptr, wave_kernel(d->size), (states + spl - 1) / spl};
+  };
+  if (const int32_t rc = ts::plan_forms(d, kBitmaps, kCtlWords, "k_table", choose, p.f); rc != TS_OK) return rc;
+  BArgs &a = p.a;
+  a.N = d->n_boards, a.T = d->n_tiles, a.Tt = d->n_targets, a.mc = d->multi_color;
+  a.states = (uint32_t)p.f.states, a.words = p.f.words, a.board_words = p.f.board_words, a.lanes_log2 = p.f.lanes_log2;
+  ts::describe_forms(p.f, p.desc);
+  p.desc.lds_bytes_max = (int32_t)ts::kMaxBlockLds;
+  p.desc.table_bytes = d->n_boards * p.f.states;
   return TS_OK;
 }
 
@@ -418,9 +294,9 @@ int32_t finish_launch() {
 extern "C" {
 
 int32_t ts_table_abi_version(void) { return TS_TABLE_ABI_VERSION; }
-int32_t ts_table_last_hip_error(void) { return t_last_hip_error; }
+int32_t ts_table_last_hip_error(void) { return ts::t_last_hip_error; }
 
-int64_t ts_table_states(const ts_dims *dims) { return table_states(dims); }
+int64_t ts_table_states(const ts_dims *dims) { return ts::checked_states(dims); }
 
 int32_t ts_describe_table_build(const ts_dims *dims, ts_table_desc *desc) {
   if (!dims || !desc) return TS_ERR_NULL;
@@ -440,14 +316,14 @@ int32_t ts_table_build(const ts_dims *dims, const ts_state *st, int32_t max_dept
   if (!st || !table || !st->blk || (dims->n_targets > 0 && !st->tgt)) return TS_ERR_NULL;
   p.a.tgt = static_cast<const uint8_t *>(st->tgt), p.a.blk = st->blk;
   p.a.table = table, p.a.max_depth = max_depth;
-  hipLaunchKernelGGL(p.kernel, dim3(p.blocks), dim3(p.threads), p.lds, static_cast<hipStream_t>(stream), p.a);
-  return finish_launch();
+  hipLaunchKernelGGL(p.f.kernel, dim3(p.f.blocks), dim3(p.f.threads), p.f.lds, static_cast<hipStream_t>(stream), p.a);
+  return ts::finish_launch();
 }
 
 int32_t ts_table_lookup(const ts_dims *dims, const ts_state *st, const uint8_t *table, int64_t n_rows, const int32_t *rows,
                         int16_t *moves, uint8_t *best, uint8_t *action, void *stream) {
   if (!dims) return TS_ERR_NULL;
-  const int64_t states = table_states(dims);
+  const int64_t states = ts::checked_states(dims);
   if (states < 0) return (int32_t)states;
   if (states == 0) return TS_ERR_LIMIT;
   if (n_rows < 0) return TS_ERR_ARG;
@@ -461,7 +337,7 @@ int32_t ts_table_lookup(const ts_dims *dims, const ts_state *st, const uint8_t *
   a.moves = moves, a.best = best, a.action = action;
   a.N = dims->n_boards, a.n_rows = n_rows, a.T = dims->n_tiles, a.states = (uint32_t)states;
   hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(kBlockThreads), 0, static_cast<hipStream_t>(stream), a);
-  return finish_launch();
+  return ts::finish_launch();
 }
 
 int64_t ts_table_tuning(int32_t key, int64_t value) {
@@ -469,8 +345,7 @@ int64_t ts_table_tuning(int32_t key, int64_t value) {
                                : key == TS_TABLE_TUNE_STATES_PER_LANE    ? &g_states_per_lane
                                : key == TS_TABLE_TUNE_BLOCK_BELOW_BOARDS ? &g_block_below_boards
                                                                          : nullptr;
-  if (!knob) return -1;
-  return value >= 0 ? knob->exchange(value, std::memory_order_relaxed) : knob->load(std::memory_order_relaxed);
+  return ts::tune(knob, value);
 }
 
 }  // extern "C"

@@ -750,7 +750,7 @@ class VecTilerSliderEnv:
         moves, bits = self.solve_bits(max_depth, with_best)
         if bits is None:
             return moves, None
-        return moves, (bits.unsqueeze(1) >> torch.arange(4, dtype=torch.uint8, device=bits.device) & 1).to(torch.bool)
+        return moves, _bit_columns(bits)
 
     def solve_bits(self, max_depth=64, with_best=True):
         """solve() with the kernel's raw second output: (moves int16 [N], best uint8 [N] with bit a set where Move a starts a
@@ -765,14 +765,7 @@ class VecTilerSliderEnv:
             raise ValueError(f"max_depth must be 0..{sc.SOLVE_MAX_DEPTH}")
         moves = self._empty(self.num_envs, torch.int16)
         best = self._empty(self.num_envs, torch.uint8) if with_best else None
-        fn = self._fns.get("ts_solve")
-        if fn is None:
-            fn = self._fns["ts_solve"] = sc.lib().ts_solve
-        with torch.cuda.device(self.device):
-            rc = fn(C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(moves), _ptr(best),
-                    torch.cuda.current_stream(self.device).cuda_stream)
-        if rc:
-            sc.check(rc, "ts_solve")
+        self._call("ts_solve", C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(moves), _ptr(best), binding=sc)
         self._sync_if_host()
         return moves, best
 
@@ -806,7 +799,8 @@ class VecTilerSliderEnv:
             raise ValueError(f"a table of {self.num_envs} boards x {states} placements takes {nbytes} bytes, above max_bytes = {int(max_bytes)}: "
                              "build it on an environment of the distinct levels and pass rows= to lookup() / expert_actions_from()")
         dist = torch.empty((self.num_envs, states), dtype=torch.uint8, device=self.device)
-        self._table_call(tc, "ts_table_build", C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(dist))
+        self._call("ts_table_build", C.byref(self._dims), C.byref(self._state), int(max_depth), _ptr(dist), binding=tc)
+        self._sync_if_host()
         return DistanceTable(dist, self.size, self.n_tiles, self.n_targets, self.multi_color, int(max_depth))
 
     def lookup(self, table, rows=None):
@@ -814,7 +808,7 @@ class VecTilerSliderEnv:
         wherever the table is complete.  `rows` int32 [N]: board n reads table row rows[n] (default: row n) - the caller's promise
         that the row was built for that board's level."""
         moves, bits = self.lookup_bits(table, rows)
-        return moves, (bits.unsqueeze(1) >> torch.arange(4, dtype=torch.uint8, device=bits.device) & 1).to(torch.bool)
+        return moves, _bit_columns(bits)
 
     def lookup_bits(self, table, rows=None):
         """lookup() with the kernel's raw second output: (moves int16 [N], best uint8 [N]), as solve_bits().  One launch, nothing else."""
@@ -833,16 +827,6 @@ class VecTilerSliderEnv:
                              f"{self.size}x{self.size} with {self.n_tiles} tiles is beyond that")
         return states
 
-    def _table_call(self, tc, name, *args):
-        fn = self._fns.get(name)
-        if fn is None:
-            fn = self._fns[name] = getattr(tc.lib(), name)
-        with torch.cuda.device(self.device):
-            rc = fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
-        if rc:
-            tc.check(rc, name)
-        self._sync_if_host()
-
     def _lookup(self, table, rows, want_moves, want_best, want_action):
         from . import _table_cabi as tc
         self._require_open()
@@ -850,8 +834,9 @@ class VecTilerSliderEnv:
         moves = self._empty(self.num_envs, torch.int16) if want_moves else None
         best = self._empty(self.num_envs, torch.uint8) if want_best else None
         action = self._empty(self.num_envs, torch.uint8) if want_action else None
-        self._table_call(tc, "ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(dist), n_rows, _ptr(rows),
-                         _ptr(moves), _ptr(best), _ptr(action))
+        self._call("ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(dist), n_rows, _ptr(rows), _ptr(moves), _ptr(best),
+                   _ptr(action), binding=tc)
+        self._sync_if_host()
         return moves, best, action
 
     # ------------------------------------------------------------------ fused rollouts (lib/libtiler_slider_rollout.so)
@@ -918,13 +903,7 @@ class VecTilerSliderEnv:
                 got["flags"] = self._flags
         out = rc.RolloutOut(*(_ptr(bound.get(f)) for f in rc.OUT_FIELDS))
         if steps and N and bound:
-            fn = self._fns.get("ts_rollout")
-            if fn is None:
-                fn = self._fns["ts_rollout"] = rc.lib().ts_rollout
-            with torch.cuda.device(self.device):
-                code = fn(C.byref(self._dims), C.byref(self._state), C.byref(cfg), C.byref(out), torch.cuda.current_stream(self.device).cuda_stream)
-            if code:
-                rc.check(code, "ts_rollout")
+            self._call("ts_rollout", C.byref(self._dims), C.byref(self._state), C.byref(cfg), C.byref(out), binding=rc)
             if advance and self.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful
                 self._call("ts_encode" if self.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(self._dims), C.byref(self._state),
                            _ptr(self._obs))
@@ -994,19 +973,20 @@ class VecTilerSliderEnv:
             vals.append(a.value)
         return self._stage_actions(torch.tensor(vals, dtype=torch.uint8))
 
-    def _call(self, name, *args):
-        """One C-ABI call on the current stream of the environment's device.  (The device context manager is entered only when
-        another device is current: with it a small launch - ts_valid_moves4 takes 5 us on the GPU - cost three times its kernel.)"""
+    def _call(self, name, *args, binding=_cabi):
+        """One C-ABI call on the current stream of the environment's device; `binding`: the library's module (_cabi, _search_cabi,
+        _table_cabi, _rollout_cabi).  (The device context manager is entered only when another device is current: with it a small
+        launch - ts_valid_moves4 takes 5 us on the GPU - cost three times its kernel.)"""
         fn = self._fns.get(name)
         if fn is None:
-            fn = self._fns[name] = getattr(_cabi.lib(), name)
+            fn = self._fns[name] = getattr(binding.lib(), name)
         if torch.cuda.current_device() == self.device.index:
             rc = fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
         else:
             with torch.cuda.device(self.device):
                 rc = fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
         if rc:
-            _cabi.check(rc, name)
+            binding.check(rc, name)
 
     def _require_open(self):
         if self._closed:
@@ -1091,4 +1071,9 @@ def _to_device(a, dtype, device):
 
 def _ptr(t):
     return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def _bit_columns(bits):
+    """bool [N, 4] of a uint8 [N] of best-move bits: column a is bit a."""
+    return (bits.unsqueeze(1) >> torch.arange(4, dtype=torch.uint8, device=bits.device) & 1).to(torch.bool)
 
