@@ -5,9 +5,10 @@ GameState, TilerSliderEnv, TilerSliderEnvFactory, TextRender — plus the batche
 VecTilerSliderEnv that is the point of this build.  Importing the package loads nothing
 native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
 lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
-lib/libtiler_slider_rollout.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._cabi import TilerSliderLibraryError, build_library
+from ._policy_cabi import build_library as build_policy_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
@@ -19,6 +20,7 @@ from .gym_wrapper import GymVecTilerSlider
 from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
 from .pipelined import PipelinedTilerSliderEnv
+from .policy import MlpPolicy
 from .render import TextRender
 from .vec_env import DistanceTable, Rollout, StepInfo, VecTilerSliderEnv
 
@@ -28,4 +30,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "StepInfo", "GymVecTilerSlider", "Level", "pack_levels", "parse_board_string", "simple_level", "build_library",
            "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError",
            "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
-           "Rollout", "build_rollout_library"]
+           "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library"]

@@ -98,13 +98,15 @@ class DistanceTable:
 class Rollout:
     """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
-    last step's); act_log, flags_log uint8 [steps, N]; pos_log cell ids [steps, T, N] (the compact form ts_encode re-encodes)."""
+    last step's); act_log, flags_log uint8 [steps, N]; pos_log cell ids [steps, T, N] (the compact form ts_encode re-encodes).
+    rollout_policy() can also log logits_log float32 [steps, N, 4] (include/tiler_slider_policy.h)."""
 
     FIELDS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags", "act_log", "flags_log", "pos_log")
-    __slots__ = FIELDS + ("steps",)
+    __slots__ = FIELDS + ("steps", "logits_log")
 
     def __init__(self, steps, **tensors):
         self.steps = int(steps)
+        self.logits_log = tensors.get("logits_log")
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
 
@@ -908,6 +910,26 @@ class VecTilerSliderEnv:
                 self._call("ts_encode" if self.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(self._dims), C.byref(self._state),
                            _ptr(self._obs))
         return Rollout(steps, **got)
+
+    # ------------------------------------------------------------------ neural-policy rollouts (lib/libtiler_slider_policy.so)
+    def policy_logits(self, policy):
+        """float32 [N, 4]: the logits of `policy` (tiler_slider_amd.MlpPolicy) on the boards as they stand - what the network gives on
+        encode_onehot().flatten(1), computed from the cell ids in one launch (include/tiler_slider_policy.h: ts_policy_logits); the
+        planes are never written.  No state is touched."""
+        from .policy import policy_logits
+        return policy_logits(self, policy)
+
+    def rollout_policy(self, steps, policy, select="sample", epsilon=0.0, seed=0, step_index=0, board_offset=0, stats=True, log=(),
+                       advance=True):
+        """rollout() with a network choosing every action, still ONE launch (include/tiler_slider_policy.h: ts_policy_rollout):
+        at every step the kernel evaluates `policy` (an MlpPolicy) on the board as it stands and plays
+          select "greedy": the lowest action among the largest logits
+                 "sample": a draw from softmax(logits), from bits 32 .. 55 of the step's draw of ts_fill_actions' stream
+        replaced by that stream's random action with probability `epsilon`.  seed, step_index, board_offset, stats, log and
+        advance are rollout()'s; `log` also accepts "logits": Rollout.logits_log float32 [steps, N, 4], the values each action was
+        chosen from.  Shapes as rollout("random"), hidden widths 1 .. 64: ValueError otherwise."""
+        from .policy import rollout_policy
+        return rollout_policy(self, steps, policy, select, epsilon, seed, step_index, board_offset, stats, log, advance)
 
     def _check_table(self, table, rows):
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
