@@ -45,6 +45,32 @@ class MlpPolicy:
             raise ValueError("both layers need a bias")
         return cls(l1.weight, l1.bias, l2.weight, l2.bias)
 
+    @classmethod
+    def from_kernel_layout(cls, w1, b1, w2, b2):
+        """From tensors already in the kernels' layout - w1 [D, H], b1 [H], w2 [H, 4], b2 [4], float32, contiguous, on one CUDA
+        device - whose storage the policy SHARES: nothing is cloned, and a later in-place change (an optimiser's step) is what the
+        next call plays.  tiler_slider_amd.PolicyNet.policy() is this on its parameters."""
+        for name, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor, got {type(t)}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32, got {t.dtype}")
+            if t.device != w1.device:
+                raise ValueError(f"{name} lives on {t.device}, w1 on {w1.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous: its storage is shared, not copied")
+        if w1.dim() != 2 or w1.shape[1] < 1 or w1.shape[1] > pc.POLICY_MAX_HIDDEN:
+            raise ValueError(f"w1 must be [D, H] with 1 <= H <= {pc.POLICY_MAX_HIDDEN}, got {tuple(w1.shape)}")
+        D, H = w1.shape
+        if tuple(b1.shape) != (H,) or tuple(w2.shape) != (H, 4) or tuple(b2.shape) != (4,):
+            raise ValueError(f"with w1 [{D}, {H}]: b1 must be [{H}], w2 [{H}, 4], b2 [4]; got {tuple(b1.shape)}, {tuple(w2.shape)}, {tuple(b2.shape)}")
+        if w1.device.type != "cuda":
+            raise ValueError(f"the network must live on the environment's GPU, got {w1.device}")
+        self = cls.__new__(cls)
+        self.hidden, self.features, self.device = int(H), int(D), w1.device
+        self.w1, self.b1, self.w2, self.b2 = w1.detach(), b1.detach(), w2.detach(), b2.detach()
+        return self
+
     def _mlp(self, env):
         """The ts_mlp of this network for `env`, validated against its shape and device."""
         D = env.onehot_channels * env.size * env.size
@@ -100,11 +126,13 @@ def rollout_policy(env, steps, policy, select="sample", epsilon=0.0, seed=0, ste
                        int(round(float(epsilon) * 2**32)))
     names = env._ROLLOUT_STATS if stats is True else () if not stats else tuple(stats)
     logs = (log,) if isinstance(log, str) else tuple(log)
-    all_logs = env._ROLLOUT_LOGS + ("logits",)
+    all_logs = env._ROLLOUT_LOGS + ("logits", "start")
     if set(names) - set(env._ROLLOUT_STATS) or set(logs) - set(all_logs):
         raise ValueError(f"stats are {env._ROLLOUT_STATS}, logs {all_logs}")
     got = {name: torch.zeros(N, dtype=torch.uint8 if name == "flags" else torch.int32, device=env.device) for name in names}
     for name in logs:
+        if name == "start":
+            continue
         shape = {"pos": (steps, env.n_tiles, N), "logits": (steps, N, 4)}.get(name, (steps, N))
         dtype = env._pos.dtype if name == "pos" else torch.float32 if name == "logits" else torch.uint8
         got[name + "_log"] = torch.zeros(shape, dtype=dtype, device=env.device)
@@ -114,6 +142,8 @@ def rollout_policy(env, steps, policy, select="sample", epsilon=0.0, seed=0, ste
         if "flags" in got:
             got["flags"] = env._flags
     out = pc.PolicyOut(*(_ptr(bound.get(f)) for f in pc.OUT_FIELDS))
+    if "start" in logs:  # the cells before the launch: with advance=True the launch overwrites the only other copy
+        got["start_pos"] = env._pos.clone()
     if steps and N and bound:
         env._call("ts_policy_rollout", C.byref(env._dims), C.byref(env._state), C.byref(mlp), C.byref(cfg), C.byref(out), binding=pc)
         if advance and env.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful

@@ -99,14 +99,16 @@ class Rollout:
     """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
     last step's); act_log, flags_log uint8 [steps, N]; pos_log cell ids [steps, T, N] (the compact form ts_encode re-encodes).
-    rollout_policy() can also log logits_log float32 [steps, N, 4] (include/tiler_slider_policy.h)."""
+    rollout_policy() can also log logits_log float32 [steps, N, 4] (include/tiler_slider_policy.h) and start_pos, cell ids [T, N]:
+    a copy of the cells taken before the launch (log "start"; with pos_log it is what trajectory_logits() reads)."""
 
     FIELDS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags", "act_log", "flags_log", "pos_log")
-    __slots__ = FIELDS + ("steps", "logits_log")
+    __slots__ = FIELDS + ("steps", "logits_log", "start_pos")
 
     def __init__(self, steps, **tensors):
         self.steps = int(steps)
         self.logits_log = tensors.get("logits_log")
+        self.start_pos = tensors.get("start_pos")
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
 
@@ -927,9 +929,22 @@ class VecTilerSliderEnv:
                  "sample": a draw from softmax(logits), from bits 32 .. 55 of the step's draw of ts_fill_actions' stream
         replaced by that stream's random action with probability `epsilon`.  seed, step_index, board_offset, stats, log and
         advance are rollout()'s; `log` also accepts "logits": Rollout.logits_log float32 [steps, N, 4], the values each action was
-        chosen from.  Shapes as rollout("random"), hidden widths 1 .. 64: ValueError otherwise."""
+        chosen from, and "start": Rollout.start_pos, a copy of the cells before the launch (what trajectory_logits() needs beside
+        "pos").  Shapes as rollout("random"), hidden widths 1 .. 64: ValueError otherwise."""
         from .policy import rollout_policy
         return rollout_policy(self, steps, policy, select, epsilon, seed, step_index, board_offset, stats, log, advance)
+
+    # ------------------------------------------------------------------ trainable policies (lib/libtiler_slider_train.so)
+    def trajectory_logits(self, net, rollout=None):
+        """float32 [K, N, 4]: the logits of `net` (a tiler_slider_amd.PolicyNet or an MlpPolicy) on every board-step of `rollout`
+        - a Rollout of rollout_policy(K, ..., log=("start", "pos")): step k's logits on the board that step was chosen on - or,
+        with rollout=None, on the boards as they stand (K = 1).  One launch (include/tiler_slider_train.h: ts_train_forward); the
+        one-hot planes are never built and no state is touched.  Given a PolicyNet whose parameters require grad (and outside
+        torch.no_grad()) the result carries a grad_fn: loss.backward() is one more launch (ts_train_backward) that fills the four
+        parameters' .grad, in float32 with float atomic adds - not bit-reproducible from run to run.  TypeError / ValueError for a
+        rollout without start_pos / pos_log, of another N or T, on another device, or a host-mapped environment."""
+        from .train import trajectory_logits
+        return trajectory_logits(self, net, rollout)
 
     def _check_table(self, table, rows):
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
