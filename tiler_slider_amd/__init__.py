@@ -6,7 +6,8 @@ VecTilerSliderEnv that is the point of this build.  Importing the package loads 
 native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
 lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
-trajectory_logits() lib/libtiler_slider_train.so, and each fails loudly if its library is missing (no CPU fallback).
+trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_returns() or trajectory_labels()
+lib/libtiler_slider_targets.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._cabi import TilerSliderLibraryError, build_library
 from ._policy_cabi import build_library as build_policy_library
@@ -15,6 +16,7 @@ from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
 from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
 from ._table_cabi import build_library as build_table_library
+from ._targets_cabi import build_library as build_targets_library
 from ._train_cabi import build_library as build_train_library
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
@@ -24,6 +26,7 @@ from .moves import Move
 from .pipelined import PipelinedTilerSliderEnv
 from .policy import MlpPolicy
 from .render import TextRender
+from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
 from .vec_env import DistanceTable, Rollout, StepInfo, VecTilerSliderEnv
 
@@ -34,4 +37,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError",
            "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
            "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library",
-           "PolicyNet", "build_train_library"]
+           "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library"]

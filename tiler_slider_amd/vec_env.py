@@ -846,6 +846,7 @@ class VecTilerSliderEnv:
     # ------------------------------------------------------------------ fused rollouts (lib/libtiler_slider_rollout.so)
     _ROLLOUT_STATS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags")
     _ROLLOUT_LOGS = ("act", "flags", "pos")
+    _ROLLOUT_START = ("start",)  # rollout() only: rollout_policy() adds its own names to _ROLLOUT_LOGS
 
     def rollout(self, steps, policy="random", actions=None, table=None, rows=None, epsilon=0.0, seed=0, step_index=0, board_offset=0,
                 stats=True, log=(), advance=True):
@@ -857,7 +858,9 @@ class VecTilerSliderEnv:
                  "table":  the expert move of `table` (build_table(); `rows` as in lookup()), replaced by the random draw with
                            probability `epsilon` and wherever the expert has no move
           stats=True: wins, finished, first_win, win_moves, reward_sum, flags (False: none; or an iterable of those names)
-          log: any of "act", "flags", "pos" - the per-step logs act_log, flags_log uint8 [steps, N], pos_log [steps, T, N]
+          log: any of "act", "flags", "pos" - the per-step logs act_log, flags_log uint8 [steps, N], pos_log [steps, T, N] - and
+                 "start": Rollout.start_pos, a copy of the cells before the launch (what trajectory_labels() and a reward on
+                 progress need beside "pos")
           advance=True: the environment moves on as `steps` calls of step() would move it (state, last flags; an observation-
                  keeping environment re-encodes its current observation once at the end).  advance=False: a playout from where the
                  boards stand; the environment is left untouched.
@@ -894,10 +897,13 @@ class VecTilerSliderEnv:
             cfg.table, cfg.n_rows, cfg.rows = _ptr(dist), n_rows, _ptr(rows)
         names = self._ROLLOUT_STATS if stats is True else () if not stats else tuple(stats)
         logs = (log,) if isinstance(log, str) else tuple(log)
-        if set(names) - set(self._ROLLOUT_STATS) or set(logs) - set(self._ROLLOUT_LOGS):
-            raise ValueError(f"stats are {self._ROLLOUT_STATS}, logs {self._ROLLOUT_LOGS}")
+        if set(names) - set(self._ROLLOUT_STATS) or set(logs) - set(self._ROLLOUT_LOGS + self._ROLLOUT_START):
+            raise ValueError(f"stats are {self._ROLLOUT_STATS}, logs {self._ROLLOUT_LOGS + self._ROLLOUT_START}")
         got = {name: torch.zeros(N, dtype=torch.uint8 if name == "flags" else torch.int32, device=self.device) for name in names}
+        start_pos = self._pos.clone() if "start" in logs else None  # before the launch: with advance=True it overwrites the only other copy
         for name in logs:
+            if name == "start":
+                continue
             shape = (steps, self.n_tiles, N) if name == "pos" else (steps, N)
             got[name + "_log"] = torch.zeros(shape, dtype=self._pos.dtype if name == "pos" else torch.uint8, device=self.device)
         bound = dict(got)
@@ -911,7 +917,7 @@ class VecTilerSliderEnv:
             if advance and self.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful
                 self._call("ts_encode" if self.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(self._dims), C.byref(self._state),
                            _ptr(self._obs))
-        return Rollout(steps, **got)
+        return Rollout(steps, **got) if start_pos is None else Rollout(steps, start_pos=start_pos, **got)
 
     # ------------------------------------------------------------------ neural-policy rollouts (lib/libtiler_slider_policy.so)
     def policy_logits(self, policy):
@@ -945,6 +951,34 @@ class VecTilerSliderEnv:
         rollout without start_pos / pos_log, of another N or T, on another device, or a host-mapped environment."""
         from .train import trajectory_logits
         return trajectory_logits(self, net, rollout)
+
+    # ------------------------------------------------------------------ trajectory targets (lib/libtiler_slider_targets.so)
+    def trajectory_returns(self, rollout, gamma=0.99, lam=1.0, values=None, last_value=None, reward=None):
+        """TrajectoryReturns(reward, adv, ret float32 [K, N], mask bool [K, N]) of a Rollout that logged its flags: per-step rewards,
+        GAE(gamma, lam) advantages and returns ret = adv + values, in ONE launch that walks each board's log backwards
+        (include/tiler_slider_targets.h: ts_traj_returns).  mask is False where a step played no transition - the board was done
+        on entry (strict mode: it stays; auto-reset: the step restarts it) or the action byte was no move; reward, adv and ret
+        are 0 there and the recursion passes over the step.  Both SUCCESS and TIMEOUT end an episode: nothing is bootstrapped
+        across them.
+          reward: a RewardWeights(step=0, win=1, timeout=0, invalid=0, dist=0, progress=0); `dist` and `progress` weigh the
+                  Manhattan reward of reward() on the cells after the step and its plain difference across the step - they need
+                  log "pos" (and "start" for progress); with both 0 the cells are never read
+          values: float32 [K, N] on the device, V(s_k) of the board step k was chosen on - contiguous, or a column view
+                  t[..., c] of a contiguous [K, N, 4] tensor, read in place (the logits of a critic PolicyNet); detached.
+                  None: 0, and with lam = 1 `ret` is the discounted return-to-go
+          last_value: float32 [N], V of the boards after the last step (None: 0)
+        Shapes as rollout("random"): ValueError otherwise.  Nothing is read from or written to the environment's state."""
+        from .targets import trajectory_returns
+        return trajectory_returns(self, rollout, gamma, lam, values, last_value, reward)
+
+    def trajectory_labels(self, rollout, table, rows=None):
+        """(moves int16 [K, N], best uint8 [K, N], action uint8 [K, N]): lookup_bits() and expert_actions_from() of `table` on every
+        board a Rollout visited - row k is the answer on the board step k was chosen on (start_pos, then pos_log[k - 1]) - in ONE
+        launch (include/tiler_slider_targets.h: ts_traj_labels).  `action` is a cross_entropy target wherever it is not 255 (the
+        expert has no move: the board is won, cannot be won, or its row lies outside the table).  The rollout needs log
+        ("start", "pos"); table and rows as lookup().  No state is touched."""
+        from .targets import trajectory_labels
+        return trajectory_labels(self, rollout, table, rows)
 
     def _check_table(self, table, rows):
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""

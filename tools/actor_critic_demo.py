@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
+episodes won per iteration.
+
+    python tools/actor_critic_demo.py [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+
+The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
+
+    rollout_policy (actor, sample)          -> start, cells, actions, flags        one launch
+    trajectory_logits(critic, out)[..., 0]  -> values, read in place (stride 4)    one launch
+    trajectory_logits(critic)[0, :, 0]      -> last_value, on the boards as they stand after the rollout    one launch
+    trajectory_returns(gamma, lam)          -> adv, ret, mask                       one launch
+    trajectory_logits(actor, out)           -> log-probabilities of the played actions; both losses' backward: one launch each
+
+The losses are plain torch on [K, N] floats: -(adv * logp(a)) and (v - ret)^2, both over the steps that played a transition.
+No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iterations", type=int, default=60)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--hidden", type=int, default=32)
+    ap.add_argument("--lr", type=float, default=1e-2)
+    ap.add_argument("--gamma", type=float, default=0.97)
+    ap.add_argument("--lam", type=float, default=0.9)
+    ap.add_argument("--log", default=None)
+    args = ap.parse_args()
+    import torch
+    from tiler_slider_amd import PolicyNet, RewardWeights, TilerSliderEnvFactory
+
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+        if args.log:
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            open(args.log, "w").write("\n".join(lines) + "\n")
+
+    dev = torch.device("cuda", 0)
+    seeds = TilerSliderEnvFactory.solvable_seeds(256, size=4, num_tiles=2, num_obstacles=2, device=dev)
+    env = TilerSliderEnvFactory.create_vec_env_from_seeds(seeds, size=4, num_tiles=2, num_obstacles=2, device=dev, max_steps=16, auto_reset=True,
+                                                          obs_dtype=None)
+    env.reset()
+    D = env.onehot_channels * 16
+    gen = torch.Generator(device=dev).manual_seed(0)
+    actor, critic = PolicyNet(D, args.hidden, dev, generator=gen), PolicyNet(D, args.hidden, dev, generator=gen)
+    opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
+    weights = RewardWeights(step=-0.01, win=1.0)
+    say(f"256 solvable 4x4 levels, {args.steps} steps per iteration, H = {args.hidden}, Adam {args.lr}, gamma {args.gamma}, lambda {args.lam}, "
+        f"reward {tuple(weights)}")
+    for it in range(args.iterations):
+        out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
+        v = env.trajectory_logits(critic, out)[..., 0]                      # [K, N], strides (4 N, 4): read in place below
+        with torch.no_grad():
+            last = env.trajectory_logits(critic)[0, :, 0].contiguous()      # the boards as they stand after the rollout
+        tr = env.trajectory_returns(out, args.gamma, args.lam, values=v, last_value=last, reward=weights)
+        live = tr.mask.float()
+        count = live.sum().clamp(min=1)
+        adv = (tr.adv - (tr.adv * live).sum() / count) * live
+        logp = torch.log_softmax(env.trajectory_logits(actor, out), dim=2)
+        played = logp.gather(2, out.act_log.clamp(max=3).long().unsqueeze(2)).squeeze(2)
+        actor_loss = -(adv * played).sum() / count
+        critic_loss = (((v - tr.ret) ** 2) * live).sum() / count
+        opt.zero_grad()
+        (actor_loss + 0.5 * critic_loss).backward()
+        opt.step()
+        share = float(out.wins.sum()) / max(1.0, float(out.finished.sum()))
+        say(f"iteration {it:3d}: episodes won {share:6.3f} ({int(out.wins.sum())} of {int(out.finished.sum())}), actor loss {float(actor_loss):8.4f}, "
+            f"critic loss {float(critic_loss):8.4f}")
+
+
+if __name__ == "__main__":
+    main()
