@@ -6,9 +6,10 @@ VecTilerSliderEnv that is the point of this build.  Importing the package loads 
 native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
 lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
-trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_returns() or trajectory_labels()
-lib/libtiler_slider_targets.so, and each fails loudly if its library is missing (no CPU fallback).
+trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
+trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, and each fails loudly if its library is missing (no CPU fallback).
 """
+from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
 from ._policy_cabi import build_library as build_policy_library
 from ._rollout_cabi import build_library as build_rollout_library
@@ -18,6 +19,7 @@ from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
 from ._table_cabi import build_library as build_table_library
 from ._targets_cabi import build_library as build_targets_library
 from ._train_cabi import build_library as build_train_library
+from .actor_critic import ActorCriticNet
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
 from .gym_wrapper import GymVecTilerSlider
@@ -37,4 +39,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "build_search_library", "SOLVE_NONE", "SOLVE_DEPTH", "TilerSliderLibraryError",
            "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
            "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library",
-           "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library"]
+           "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
+           "ActorCriticNet", "build_ac_library"]

@@ -133,9 +133,32 @@ class _TrajectoryLogits(torch.autograd.Function):
         return (None, *ctx.samples.backward(*ctx.saved_tensors, dlogits))
 
 
+def _trajectory_cells(env, rollout):
+    """(first, pos_log, steps) of the samples of `rollout` - or of the boards as they stand (rollout=None: steps = 1) -, checked
+    against the environment: what trajectory_logits() and trajectory_outputs() share."""
+    from .vec_env import Rollout
+    T, N = env.n_tiles, env.num_envs
+    if rollout is None:
+        return env._pos, None, 1
+    if not isinstance(rollout, Rollout):
+        raise TypeError(f"rollout must be a Rollout (rollout_policy(..., log=('start', 'pos'))), got {type(rollout)}")
+    if rollout.start_pos is None or rollout.pos_log is None:
+        raise ValueError("the rollout must have logged its start and its cells: rollout_policy(..., log=('start', 'pos'))")
+    first, pos_log = rollout.start_pos, rollout.pos_log
+    steps = int(pos_log.shape[0]) if pos_log.dim() == 3 else -1
+    if steps < 1 or tuple(first.shape) != (T, N) or tuple(pos_log.shape) != (steps, T, N):
+        raise ValueError(f"the rollout's start_pos {tuple(first.shape)} and pos_log {tuple(pos_log.shape)} are not [{T}, {N}] and "
+                         f"[steps >= 1, {T}, {N}] of this environment")
+    for t in (first, pos_log):
+        if t.device != env.device:
+            raise ValueError(f"the rollout lives on {t.device}, the environment on {env.device}")
+        if t.dtype != env._pos.dtype or not t.is_contiguous():
+            raise ValueError(f"the rollout's cells must be contiguous {env._pos.dtype}")
+    return first, pos_log, steps
+
+
 def trajectory_logits(env, net, rollout=None):
     """VecTilerSliderEnv.trajectory_logits: see there."""
-    from .vec_env import Rollout
     if isinstance(net, PolicyNet):
         policy = net.policy()
     elif isinstance(net, MlpPolicy):
@@ -143,24 +166,7 @@ def trajectory_logits(env, net, rollout=None):
     else:
         raise TypeError(f"expected a PolicyNet or an MlpPolicy, got {type(net)}")
     _prepare(env, policy)  # the environment, the shape, the width, the features and the device
-    T, N = env.n_tiles, env.num_envs
-    if rollout is None:
-        first, pos_log, steps = env._pos, None, 1
-    else:
-        if not isinstance(rollout, Rollout):
-            raise TypeError(f"rollout must be a Rollout (rollout_policy(..., log=('start', 'pos'))), got {type(rollout)}")
-        if rollout.start_pos is None or rollout.pos_log is None:
-            raise ValueError("the rollout must have logged its start and its cells: rollout_policy(..., log=('start', 'pos'))")
-        first, pos_log = rollout.start_pos, rollout.pos_log
-        steps = int(pos_log.shape[0]) if pos_log.dim() == 3 else -1
-        if steps < 1 or tuple(first.shape) != (T, N) or tuple(pos_log.shape) != (steps, T, N):
-            raise ValueError(f"the rollout's start_pos {tuple(first.shape)} and pos_log {tuple(pos_log.shape)} are not [{T}, {N}] and "
-                             f"[steps >= 1, {T}, {N}] of this environment")
-        for t in (first, pos_log):
-            if t.device != env.device:
-                raise ValueError(f"the rollout lives on {t.device}, the environment on {env.device}")
-            if t.dtype != env._pos.dtype or not t.is_contiguous():
-                raise ValueError(f"the rollout's cells must be contiguous {env._pos.dtype}")
+    first, pos_log, steps = _trajectory_cells(env, rollout)
     wants_grad = isinstance(net, PolicyNet) and torch.is_grad_enabled() and any(p.requires_grad for p in (net.w1, net.b1, net.w2, net.b2))
     if not wants_grad:
         return _Samples(env, first, pos_log, steps).forward(policy.w1, policy.b1, policy.w2, policy.b2)

@@ -952,6 +952,17 @@ class VecTilerSliderEnv:
         from .train import trajectory_logits
         return trajectory_logits(self, net, rollout)
 
+    # ------------------------------------------------------------------ the actor-critic network (lib/libtiler_slider_ac.so)
+    def trajectory_outputs(self, net, rollout=None):
+        """(logits float32 [K, N, 4], values float32 [K, N]) of `net` (a tiler_slider_amd.ActorCriticNet) on every board-step of
+        `rollout`, or with rollout=None on the boards as they stand (K = 1: values[0] is trajectory_returns()' last_value).
+        trajectory_logits() with a value head on the same hidden layer: ONE launch for both (include/tiler_slider_ac.h:
+        ts_ac_forward), and where parameters require grad both results carry the grad_fn of one function whose backward is ONE
+        launch (ts_ac_backward) taking both cotangents - a loss that uses only one of the two gives the other a zero one.
+        `values` feeds trajectory_returns(values=...) as it is.  Checks and errors as trajectory_logits()."""
+        from .actor_critic import trajectory_outputs
+        return trajectory_outputs(self, net, rollout)
+
     # ------------------------------------------------------------------ trajectory targets (lib/libtiler_slider_targets.so)
     def trajectory_returns(self, rollout, gamma=0.99, lam=1.0, values=None, last_value=None, reward=None):
         """TrajectoryReturns(reward, adv, ret float32 [K, N], mask bool [K, N]) of a Rollout that logged its flags: per-step rewards,

@@ -2,7 +2,7 @@
 """An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
 episodes won per iteration.
 
-    python tools/actor_critic_demo.py [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+    python tools/actor_critic_demo.py [--shared] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
 
 The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
 
@@ -11,6 +11,15 @@ The critic is a second PolicyNet whose output column 0 is read as V(s) (DESIGN.m
     trajectory_logits(critic)[0, :, 0]      -> last_value, on the boards as they stand after the rollout    one launch
     trajectory_returns(gamma, lam)          -> adv, ret, mask                       one launch
     trajectory_logits(actor, out)           -> log-probabilities of the played actions; both losses' backward: one launch each
+
+With --shared the actor and the critic are ONE ActorCriticNet: the hidden layer feeds four logits and a
+value head of its own, and an iteration is
+
+    rollout_policy (net.policy(), sample)   -> start, cells, actions, flags        one launch
+    trajectory_outputs(net, out)            -> logits and values                    one launch
+    trajectory_outputs(net)[1][0]           -> last_value                           one launch
+    trajectory_returns(gamma, lam)          -> adv, ret, mask                       one launch
+    both losses' backward                                                           one launch
 
 The losses are plain torch on [K, N] floats: -(adv * logp(a)) and (v - ret)^2, both over the steps that played a transition.
 No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
@@ -31,10 +40,11 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--gamma", type=float, default=0.97)
     ap.add_argument("--lam", type=float, default=0.9)
+    ap.add_argument("--shared", action="store_true", help="one ActorCriticNet with a shared trunk instead of two PolicyNets")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
     import torch
-    from tiler_slider_amd import PolicyNet, RewardWeights, TilerSliderEnvFactory
+    from tiler_slider_amd import ActorCriticNet, PolicyNet, RewardWeights, TilerSliderEnvFactory
 
     lines = []
 
@@ -52,21 +62,30 @@ def main():
     env.reset()
     D = env.onehot_channels * 16
     gen = torch.Generator(device=dev).manual_seed(0)
-    actor, critic = PolicyNet(D, args.hidden, dev, generator=gen), PolicyNet(D, args.hidden, dev, generator=gen)
-    opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
+    if args.shared:
+        actor = critic = ActorCriticNet(D, args.hidden, dev, generator=gen)
+        opt = torch.optim.Adam(actor.parameters(), lr=args.lr)
+    else:
+        actor, critic = PolicyNet(D, args.hidden, dev, generator=gen), PolicyNet(D, args.hidden, dev, generator=gen)
+        opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
     weights = RewardWeights(step=-0.01, win=1.0)
-    say(f"256 solvable 4x4 levels, {args.steps} steps per iteration, H = {args.hidden}, Adam {args.lr}, gamma {args.gamma}, lambda {args.lam}, "
+    say(f"{'one ActorCriticNet (shared trunk)' if args.shared else 'two PolicyNets'}: 256 solvable 4x4 levels, {args.steps} steps per iteration, H = {args.hidden}, Adam {args.lr}, gamma {args.gamma}, lambda {args.lam}, "
         f"reward {tuple(weights)}")
     for it in range(args.iterations):
         out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
-        v = env.trajectory_logits(critic, out)[..., 0]                      # [K, N], strides (4 N, 4): read in place below
-        with torch.no_grad():
-            last = env.trajectory_logits(critic)[0, :, 0].contiguous()      # the boards as they stand after the rollout
+        if args.shared:
+            logits, v = env.trajectory_outputs(actor, out)                      # [K, N, 4] and [K, N], one launch
+            with torch.no_grad():
+                last = env.trajectory_outputs(actor)[1][0]                      # the boards as they stand after the rollout
+        else:
+            v = env.trajectory_logits(critic, out)[..., 0]                      # [K, N], strides (4 N, 4): read in place below
+            with torch.no_grad():
+                last = env.trajectory_logits(critic)[0, :, 0].contiguous()      # the boards as they stand after the rollout
         tr = env.trajectory_returns(out, args.gamma, args.lam, values=v, last_value=last, reward=weights)
         live = tr.mask.float()
         count = live.sum().clamp(min=1)
         adv = (tr.adv - (tr.adv * live).sum() / count) * live
-        logp = torch.log_softmax(env.trajectory_logits(actor, out), dim=2)
+        logp = torch.log_softmax(logits if args.shared else env.trajectory_logits(actor, out), dim=2)
         played = logp.gather(2, out.act_log.clamp(max=3).long().unsqueeze(2)).squeeze(2)
         actor_loss = -(adv * played).sum() / count
         critic_loss = (((v - tr.ret) ** 2) * live).sum() / count
