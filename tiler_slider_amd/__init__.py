@@ -3,7 +3,7 @@
 Export names follow the reference package (ref: explainrl/environment/__init__.py:13-25):
 GameState, TilerSliderEnv, TilerSliderEnvFactory, TextRender — plus the batched
 VecTilerSliderEnv that is the point of this build.  Importing the package loads nothing
-native; constructing an environment loads lib/libtiler_slider_hip.so, the first solve()
+native; constructing an environment loads lib/libtiler_slider_hip.so and lib/libtiler_slider_update.so, the first solve()
 lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
 trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
@@ -19,6 +19,7 @@ from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
 from ._table_cabi import build_library as build_table_library
 from ._targets_cabi import build_library as build_targets_library
 from ._train_cabi import build_library as build_train_library
+from ._update_cabi import build_library as build_update_library
 from .actor_critic import ActorCriticNet
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
@@ -40,4 +41,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
            "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library",
            "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
-           "ActorCriticNet", "build_ac_library"]
+           "ActorCriticNet", "build_ac_library", "build_update_library"]

@@ -53,7 +53,7 @@ class StepOut(C.Structure):
 OP_STEP, OP_RESET, OP_OBSERVE = 0, 1, 2
 HANDOFF_CELLS, HANDOFF_REWARD, HANDOFF_STEP_COUNT = 0x1, 0x2, 0x4
 OUT_OBS, OUT_REWARD, OUT_ONEHOT, OUT_VALID, OUT_OBS_U8, OUT_VALID4, OUT_FLAGS = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
-KERNEL_NAMES = {0: "none", 1: "k_small", 2: "k_multi", 3: "k_deal", 4: "k_lines", 5: "k_state"}
+KERNEL_NAMES = {0: "none", 1: "k_small", 2: "k_multi", 3: "k_deal", 4: "k_lines", 5: "k_state", 6: "k_step_update"}
 
 
 class Desc(C.Structure):
@@ -75,7 +75,12 @@ class LaunchDesc(Desc):
 
 
 def describe_launch(dims, op=OP_STEP, outputs=OUT_OBS):
-    """dict of ts_describe_launch(dims, op, outputs): the launch ts_step / ts_reset / ts_encode ... would make.  No GPU needed."""
+    """dict of ts_describe_launch(dims, op, outputs): the launch ts_step / ts_reset / ts_encode ... would make.  No GPU needed.
+    A Dims object that an environment has marked `step_in_place` (VecTilerSliderEnv(obs_update=...): its steps go through
+    ts_step_update) answers OP_STEP with ts_describe_step_update's record instead: the kernel that actually runs."""
+    if op == OP_STEP and getattr(dims, "step_in_place", False):
+        from . import _update_cabi
+        return _update_cabi.describe_step_update(dims, outputs & ~OUT_FLAGS)
     desc = LaunchDesc()
     check(lib().ts_describe_launch(C.byref(dims), op, outputs, C.byref(desc)), "ts_describe_launch")
     return desc.as_dict()

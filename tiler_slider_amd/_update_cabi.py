@@ -1,0 +1,55 @@
+"""ctypes binding of lib/libtiler_slider_update.so — the in-place step's C-ABI declared in include/tiler_slider_update.h.
+
+A ninth library beside the step, search, table, rollout, policy, train, targets and actor-critic libraries (the step library is
+pinned symbol by symbol and kernel by kernel, so the in-place kernels live in their own).  Same rules as _cabi.py: built through
+_cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library
+is missing or does not load, every entry point raises.
+"""
+import ctypes as C
+import os
+
+from . import _cabi
+from ._cabi import Dims, LaunchDesc, State, StepOut
+
+SRC = os.path.join(_cabi._PKG, "csrc", "ts_update.hip")
+HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_update.h")]
+LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_update.so")
+
+ABI_VERSION = 1
+UPDATE_MAX_SIZE, UPDATE_MAX_TILES = 8, 8
+KERNEL_UPDATE = 6
+MIN_KERNELS = 32  # k_step_update<1 .. 8, 2 / 8, float32 / uint8>: what compile_guarded must find in the device assembly
+
+EXPORTS = ("ts_update_abi_version", "ts_update_last_hip_error", "ts_update_supported", "ts_step_update", "ts_describe_step_update")
+
+
+def _declare(L):
+    P, DP, SP = C.c_void_p, C.POINTER(Dims), C.POINTER(State)
+    L.ts_update_supported.argtypes = [DP, C.c_uint32]
+    L.ts_update_supported.restype = C.c_int32
+    L.ts_step_update.argtypes = [DP, SP, P, C.c_uint32, C.POINTER(StepOut), P, P]
+    L.ts_step_update.restype = C.c_int32
+    L.ts_describe_step_update.argtypes = [DP, C.c_uint32, C.POINTER(LaunchDesc)]
+    L.ts_describe_step_update.restype = C.c_int32
+
+
+_lib = None
+build_library, lib, check = _cabi.bind(__name__, "update ", "ts_update_", _declare)
+
+
+def update_supported(dims, outputs):
+    """ts_update_supported(dims, outputs) as a bool: False for a shape or a set of outputs the in-place step does not take;
+    raises for invalid dims.  No GPU needed."""
+    rc = lib().ts_update_supported(C.byref(dims), int(outputs))
+    if rc in (_cabi.ERR_LIMIT, _cabi.ERR_ARG):
+        return False
+    check(rc, "ts_update_supported")
+    return True
+
+
+def describe_step_update(dims, outputs=_cabi.OUT_OBS):
+    """dict of ts_describe_step_update(dims, outputs): the launch ts_step_update would make, in the record of
+    _cabi.describe_launch.  No GPU needed."""
+    desc = LaunchDesc()
+    check(lib().ts_describe_step_update(C.byref(dims), int(outputs), C.byref(desc)), "ts_describe_step_update")
+    return desc.as_dict()

@@ -148,4 +148,5 @@ def rollout_policy(env, steps, policy, select="sample", epsilon=0.0, seed=0, ste
         env._call("ts_policy_rollout", C.byref(env._dims), C.byref(env._state), C.byref(mlp), C.byref(cfg), C.byref(out), binding=pc)
         if advance and env.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful
             env._call("ts_encode" if env.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(env._dims), C.byref(env._state), _ptr(env._obs))
+            env._sync_shown()
     return Rollout(steps, **got)

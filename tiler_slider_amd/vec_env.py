@@ -18,7 +18,7 @@ from collections.abc import Mapping
 import numpy as np
 import torch
 
-from . import _cabi
+from . import _cabi, _update_cabi
 from .levels import blk_words, cell_dtype, pack_levels
 from .moves import Move
 
@@ -122,7 +122,8 @@ class VecTilerSliderEnv:
     def __init__(self, size, blocked_locations=None, initial_locations=None, target_locations=None,
                  multi_color=False, max_steps=100, *, device=None, strict=False, auto_reset=False,
                  with_reward=False, with_onehot=False, with_valid_moves=False, obs_dtype="float32",
-                 host_mapped=False, obs_buffers=1, placement_trials=0, output_memory="contiguous", obs_candidates=None):
+                 host_mapped=False, obs_buffers=1, placement_trials=0, output_memory="contiguous", obs_candidates=None,
+                 obs_update="auto"):
         """blocked/initial/target_locations: one list of (row, col) per board.
 
         strict      : raise the reference's RuntimeError when any board is stepped after done
@@ -174,6 +175,19 @@ class VecTilerSliderEnv:
                       policy by 2 %; k > 1: the same for up to k candidate sets of output buffers, keeping the best set
                       (k times the output memory during construction).  No effect on results.  `placement_report` holds
                       the timings, the static policy's among them.
+        obs_update  : how step() keeps the observation buffer current.  "full": every step rewrites the whole buffer (ts_step).
+                      "auto" (default): where the in-place step takes the shape and the outputs (boards up to 8x8 with 1 .. 8
+                      tiles and at most 8 targets, a float32 or uint8 observation, no one-hot planes, no legality mask:
+                      include/tiler_slider_update.h), with obs_buffers = 1 and device buffers, and inside the domain that measured
+                      faster (in_place_pays: from 786,432 boards on while the observation buffer fits the Infinity Cache - the
+                      library's cache threshold, 256 MiB; beyond it from 524,288 boards on with at least 170 bytes of
+                      observation per tile),
+                      a step stores only the cells of the tile channel that change
+                      (ts_step_update: 1M 4x4 boards 20.7 us instead of 30.2) - the obstacle and target
+                      channels are level data that reset() wrote and no step changes.  The observation step() returns is
+                      then THE ENVIRONMENT'S BUFFER, UPDATED IN PLACE: writing into it corrupts every later observation
+                      until the next reset().  Clone it to change it, or pass obs_update="full".  "inplace": in place wherever the shape and the outputs allow it, whatever the
+                      size of the buffer (ValueError elsewhere); for measurements (tools/update_ab.py).  Results never differ.
         host_mapped : keep every buffer in pinned host memory that the GPU reads and writes in
                       place (zero-copy).  For a handful of boards driven move by move from Python
                       (the one-board adapters): a step is then one launch plus one stream
@@ -185,7 +199,8 @@ class VecTilerSliderEnv:
         target_locations = target_locations if target_locations is not None else [[] for _ in range(n)]
         blk, init, tgt = pack_levels(size, blocked_locations, initial_locations or [], target_locations)
         self._setup(size, blk, init, tgt, multi_color, max_steps, device, strict, auto_reset, with_reward,
-                    with_onehot, with_valid_moves, obs_dtype, host_mapped, obs_buffers, placement_trials, output_memory, obs_candidates)
+                    with_onehot, with_valid_moves, obs_dtype, host_mapped, obs_buffers, placement_trials, output_memory, obs_candidates,
+                    obs_update)
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -198,7 +213,7 @@ class VecTilerSliderEnv:
                     kw.pop("auto_reset", False), kw.pop("with_reward", False), kw.pop("with_onehot", False),
                     kw.pop("with_valid_moves", False), kw.pop("obs_dtype", "float32"), kw.pop("host_mapped", False),
                     kw.pop("obs_buffers", 1), kw.pop("placement_trials", 0), kw.pop("output_memory", "contiguous"),
-                    kw.pop("obs_candidates", None))
+                    kw.pop("obs_candidates", None), kw.pop("obs_update", "auto"))
         if kw:
             raise TypeError(f"unexpected arguments {sorted(kw)}")
         if validate:
@@ -289,7 +304,7 @@ class VecTilerSliderEnv:
     # ------------------------------------------------------------------ setup
     def _setup(self, size, blk, init, tgt, multi_color, max_steps, device, strict, auto_reset, with_reward,
                with_onehot, with_valid_moves, obs_dtype="float32", host_mapped=False, obs_buffers=1, placement_trials=0,
-               output_memory="contiguous", obs_candidates=None):
+               output_memory="contiguous", obs_candidates=None, obs_update="auto"):
         L = _cabi.lib()  # raises when the HIP library is missing: no fallback
         self._fns = {}
         self.device = _resolve_device(device)
@@ -358,13 +373,18 @@ class VecTilerSliderEnv:
             self._state.lines = _ptr(self._lines)
         self._mode = _cabi.MODE_AUTORESET if self.auto_reset else _cabi.MODE_STRICT
         self._bind_outputs()
+        self._setup_obs_update(obs_update)
         self.placement_report = self.observation_placement_report = None
         if obs_candidates is None:  # two large output streams: the observation buffer's place decides between two speeds
             obs_candidates = 16 if (self._onehot is not None and self.obs_dtype is not None and self._outputs_beyond_cache and not self.host_mapped) else 0
-        if int(obs_candidates) > 1:
+        # (both rate the full-write kernel: nothing to choose for an environment that steps in place)
+        if int(obs_candidates) > 1 and not self._in_place:
             self._choose_observation_buffers(int(obs_candidates))
         if int(placement_trials) >= 1:
-            self._tune_placement(int(placement_trials))
+            if self._in_place:
+                self.placement_report = {"skipped": "steps in place"}
+            else:
+                self._tune_placement(int(placement_trials))
         self.observation_shape = (self.size, self.size, 3)  # per board, environment.py:59
         self._started = False
         self._closed = False
@@ -377,6 +397,61 @@ class VecTilerSliderEnv:
         self._obs_slot = 0
         self._obs = self._obs_ring[0]
         self._out = self._outs[0]
+
+    def _setup_obs_update(self, obs_update):
+        """obs_update of the constructor: does step() go through ts_step_update?  `_shown` [T, N] holds the cells the observation
+        buffer displays (include/tiler_slider_update.h); `_obs_current` says that buffer and `_shown` agree - a full write
+        (reset(), or the first step of an environment that was never reset) followed by _sync_shown() makes it so."""
+        if obs_update not in ("auto", "full", "inplace"):
+            raise ValueError("obs_update must be 'auto', 'full' or 'inplace'")
+        self.obs_update = obs_update
+        self._in_place, self._shown, self._obs_current = False, None, False
+        if obs_update == "full":
+            return
+        f32 = self.obs_dtype == torch.float32
+        outputs = ((_cabi.OUT_OBS if f32 else 0) | (_cabi.OUT_OBS_U8 if self.obs_dtype == torch.uint8 else 0)
+                   | (_cabi.OUT_REWARD if self._reward is not None else 0) | (_cabi.OUT_ONEHOT if self._onehot is not None else 0)
+                   | (_cabi.OUT_VALID | _cabi.OUT_VALID4 if self._valid is not None else 0))
+        able = (self.num_envs > 0 and len(self._obs_ring) == 1 and not self.host_mapped
+                and _update_cabi.update_supported(self._dims, outputs))
+        if obs_update == "inplace" and not able:
+            raise ValueError("obs_update='inplace' needs boards up to 8x8 with 1 .. 8 tiles and at most 8 targets, one float32 or uint8 "
+                             "observation buffer in device memory, and neither one-hot planes nor the legality mask")
+        obs_bytes = self._obs.numel() * self._obs.element_size() if self._obs is not None else 0
+        self._in_place = able and (obs_update == "inplace" or self.in_place_pays(obs_bytes, self.num_envs, self.n_tiles))
+        if self._in_place:
+            self._shown = torch.empty_like(self._pos)
+            self._dims.step_in_place = True  # _cabi.describe_launch(dims, OP_STEP, ...) then names the kernel that runs
+
+    _IN_PLACE_MIN_BOARDS = 3 << 18         # 786,432: inside the cache
+    _IN_PLACE_MIN_BOARDS_BEYOND = 1 << 19  # 524,288: beyond it
+    _IN_PLACE_BYTES_PER_TILE = 170
+
+    @classmethod
+    def in_place_pays(cls, obs_bytes, n_boards, n_tiles):
+        """The domain of obs_update="auto", as measured (profiles/update_ab.log; us per step in place / full).
+        INSIDE the Infinity Cache - the threshold the full-write kernels switch their own launch forms by - 4x4 boards with 2
+        tiles: up to 131,072 boards both paths sit at the launch floor (6.1 / 6.3); 262,144 boards 6.8 / 9.6, 524,288 boards
+        12.0 / 16.6, 786,432 boards 15.9 / 23.0, 1,048,576 boards 20.6 / 30.2.  In place is taken from 786,432 boards on: up to
+        524,288 boards default environments keep the full-write kernels, which tests/test_kernel_instantiations.py reaches
+        through env.step and asserts by name.  BEYOND the cache every scattered store becomes a partial-line write to HBM and
+        costs about a whole line at ~5 TB/s against a full write streaming at ~7 TB/s, 0.95 stores per tile and step: in
+        place pays where a board has at least 128 x 0.95 x 7 / 5 = 170 bytes of observation per tile.  8x8 boards with 4 tiles
+        (192 B per tile; 524,288 boards, 384 MiB) 47.7 / 56.8; 5x5 with 2 tiles (150 B per tile, 300 MiB) 47.4 / 44.4; 4x4 with
+        2 tiles (96 B per tile) 201 / 116 at 768 MiB and 878 / 638 at 3 GiB.  That branch rests on one winning shape."""
+        if obs_bytes <= _cabi.lib().ts_tuning(_cabi.TUNE_NT_THRESHOLD_BYTES, -1):
+            return n_boards >= cls._IN_PLACE_MIN_BOARDS
+        return n_boards >= cls._IN_PLACE_MIN_BOARDS_BEYOND and obs_bytes // n_boards >= cls._IN_PLACE_BYTES_PER_TILE * n_tiles
+
+    def _sync_shown(self, stream=None):
+        """After a full write of the observation buffer from the current cells: the buffer displays `pos`."""
+        if self._in_place:
+            if stream is None:
+                self._shown.copy_(self._pos)
+            else:
+                with torch.cuda.stream(stream):
+                    self._shown.copy_(self._pos)
+            self._obs_current = True
 
     def _choose_observation_buffers(self, k):
         """`obs_candidates=k`: per slot of the observation ring, the fastest of up to k candidate buffers (see the constructor)."""
@@ -599,6 +674,7 @@ class VecTilerSliderEnv:
             self._call("ts_reset", C.byref(self._dims), C.byref(self._state), None)
             if self.obs_dtype is not None:
                 self._call("ts_encode_u8", C.byref(self._dims), C.byref(self._state), _ptr(self._obs))
+        self._sync_shown()
         self._sync_if_host()
         self._started = True
         return self._obs
@@ -606,7 +682,10 @@ class VecTilerSliderEnv:
     def step(self, actions):
         """actions: uint8/int tensor [N] of Move values, a numpy array, or a list of Move.
         Returns (obs, done, info).  `obs` is the environment's own buffer, overwritten by the
-        next step()/reset() — clone it to keep it."""
+        next step()/reset() — clone it to keep it.  Where the environment steps in place (obs_update:
+        the default for large batches of small boards) the next step UPDATES that buffer instead of
+        rewriting it: writing into it corrupts later observations - clone it, or construct with
+        obs_update="full"."""
         self._require_open()
         if not self._started:
             raise RuntimeError("Call reset() before step().")
@@ -620,9 +699,20 @@ class VecTilerSliderEnv:
         return self._obs, self._done.view(torch.bool), self._info()
 
     def step_async(self, act=None, stream=None):
-        """The bare launch: one ts_step on the current stream (or on `stream`, a torch.cuda.Stream), no
-        validation, no sync.  `act` is a uint8 device tensor [N] (default: the env's own action buffer)."""
+        """The bare launch: one ts_step - or, where the environment steps in place (obs_update), one ts_step_update, which
+        stores only the observation cells that change: the buffer is the environment's, do not write into it - on the current
+        stream (or on `stream`, a torch.cuda.Stream), no validation, no sync.  `act` is a uint8 device tensor [N] (default: the
+        env's own action buffer)."""
         a = self._actions if act is None else act
+        if self._obs_current:  # in place (_mode stays what the rollout libraries read)
+            if stream is None:
+                self._call("ts_step_update", C.byref(self._dims), C.byref(self._state), a.data_ptr(), self._mode, C.byref(self._out),
+                           self._shown.data_ptr(), binding=_update_cabi)
+            else:
+                _update_cabi.check(_update_cabi.lib().ts_step_update(C.byref(self._dims), C.byref(self._state), a.data_ptr(), self._mode,
+                                                                     C.byref(self._out), self._shown.data_ptr(), stream.cuda_stream),
+                                   "ts_step_update")
+            return
         if len(self._obs_ring) > 1:  # next observation buffer: the previous one stays intact
             self._obs_slot = (self._obs_slot + 1) % len(self._obs_ring)
             self._obs, self._out = self._obs_ring[self._obs_slot], self._outs[self._obs_slot]
@@ -632,6 +722,7 @@ class VecTilerSliderEnv:
         else:  # no stream context switch from Python: the handle goes straight into the C-ABI
             _cabi.check(_cabi.lib().ts_step(C.byref(self._dims), C.byref(self._state), a.data_ptr(), self._mode,
                                             C.byref(self._out), stream.cuda_stream), "ts_step")
+        self._sync_shown(stream)  # in place, never reset: this full write is what the following steps update
 
     def capture_steps(self, action_buffers):
         """Capture one ts_step per action buffer (uint8 device tensors [N], read at replay time)
@@ -652,6 +743,10 @@ class VecTilerSliderEnv:
             if not (isinstance(b, torch.Tensor) and b.dtype == torch.uint8 and b.device == self.device
                     and b.shape == (self.num_envs,) and b.is_contiguous()):
                 raise TypeError("action buffers must be contiguous uint8 device tensors of shape [N]")
+        if self._in_place and not self._obs_current:
+            # never reset: the full write that the in-place steps update happens now, not inside the graph - the buffer and
+            # `_shown` then agree whether the next launch is a replay or an eager step
+            self.encode(out=self._obs)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(self.device)
@@ -717,6 +812,8 @@ class VecTilerSliderEnv:
             out = self._empty((self.num_envs, self.size, self.size, 3), self.obs_dtype or torch.float32)
         name = "ts_encode" if out.dtype == torch.float32 else "ts_encode_u8"
         self._call(name, C.byref(self._dims), C.byref(self._state), out.data_ptr())
+        if self._obs is not None and out.data_ptr() == self._obs.data_ptr():  # the buffer itself or a view of it
+            self._sync_shown()
         self._sync_if_host()
         return out
 
@@ -917,6 +1014,7 @@ class VecTilerSliderEnv:
             if advance and self.obs_dtype is not None:  # one encode into the current buffer: env._obs stays truthful
                 self._call("ts_encode" if self.obs_dtype == torch.float32 else "ts_encode_u8", C.byref(self._dims), C.byref(self._state),
                            _ptr(self._obs))
+                self._sync_shown()
         return Rollout(steps, **got) if start_pos is None else Rollout(steps, start_pos=start_pos, **got)
 
     # ------------------------------------------------------------------ neural-policy rollouts (lib/libtiler_slider_policy.so)

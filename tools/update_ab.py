@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Times the in-place step (include/tiler_slider_update.h) against the full-write step on one GPU: where is
+VecTilerSliderEnv(obs_update="auto") allowed to step in place?
+
+    python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1] [--only cfg1_1m]
+
+Per shape two environments on the same levels (bench.py's LEVEL_SEED, multi colour, auto-reset, max_steps 2**30) and the same
+sixteen action buffers (ACTION_SEED): obs_update="inplace" (ts_step_update whatever the size of the buffer) and obs_update="full"
+(ts_step).  Each is timed with HIP events on the launch stream over 200 steps after a reset and 50 warm-up steps, --rounds times,
+the two taking turns; the line gives every round, the medians and their ratio, and what "auto" chooses for the shape.  Before a
+shape is timed the two environments are compared after 20 steps (observation, flags, cells): nothing is timed that computes
+something else.
+
+--store sc1 loads a build of the library whose scattered observation stores are agent-scope stores (-DTS_UPDATE_STORE_SC1, built
+into build/variants/ through the guarded build on first use) instead of the shipped plain stores.
+profiles/update_ab.log is where a run of this script belongs; run it under `timeout`.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LEVEL_SEED = 0x715311DE
+ACTION_SEED = 0xAC710005
+# name: (size, tiles, obstacles, boards)
+SHAPES = {
+    "cfg1_4k": (4, 2, 2, 4096),
+    "cfg1_64k": (4, 2, 2, 65536),
+    "cfg1_128k": (4, 2, 2, 1 << 17),
+    "cfg1_256k": (4, 2, 2, 1 << 18),
+    "cfg1_512k": (4, 2, 2, 1 << 19),
+    "cfg1_768k": (4, 2, 2, 3 << 18),
+    "cfg1_1m": (4, 2, 2, 1 << 20),
+    "cfg1_4m": (4, 2, 2, 4 << 20),
+    "cfg1_16m": (4, 2, 2, 16 << 20),
+    "8x8_4_512k": (8, 4, 6, 524288),
+    "5x5_2_1m": (5, 2, 3, 1 << 20),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log", default=None)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--store", choices=("plain", "sc1"), default="plain")
+    ap.add_argument("--only", default=None, help="comma-separated names of SHAPES")
+    ap.add_argument("--clock-warmup-ms", type=float, default=300.0)
+    args = ap.parse_args()
+    import torch
+    from tiler_slider_amd import VecTilerSliderEnv, _cabi, _update_cabi
+
+    if args.store == "sc1":
+        variant = os.path.join(ROOT, "build", "variants", "libtiler_slider_update_sc1.so")
+        if not os.path.exists(variant):
+            _cabi.compile_guarded(_update_cabi.SRC, variant, defines=("-DTS_UPDATE_STORE_SC1=1",), work=os.path.dirname(variant),
+                                  min_kernels=_update_cabi.MIN_KERNELS)
+        _update_cabi.LIB_PATH = variant  # before the first lib(): this process steps with the variant
+
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+        if args.log:  # rewritten at every line: what was measured survives a run that ends early
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            open(args.log, "w").write("\n".join(lines) + "\n")
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    L = _cabi.lib()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    say(f"# tools/update_ab.py --store {args.store}: {args.steps} timed steps after {args.warmup} warm-up steps, HIP events, us per step; "
+        f"{torch.cuda.get_device_name(dev)}")
+    say(f"# library: {os.path.relpath(_update_cabi.LIB_PATH, ROOT)}")
+    say("# shape            boards  obs MiB  kernel (in place)              in place, rounds        full, rounds            in place  full    full / in place  auto")
+
+    def timed(env, ring):
+        for i in range(args.warmup):
+            env.step_async(ring[i & 15])
+        e0.record()
+        for i in range(args.steps):
+            env.step_async(ring[i & 15])
+        e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1) * 1e3 / args.steps
+
+    names = args.only.split(",") if args.only else list(SHAPES)
+    for name in names:
+        S, T, K, n = SHAPES[name]
+        kw = dict(size=S, num_tiles=T, num_obstacles=K, seed=LEVEL_SEED, multi_color=True, max_steps=2**30, device=dev, auto_reset=True)
+        inplace = VecTilerSliderEnv.random(n, obs_update="inplace", **kw)
+        full = VecTilerSliderEnv.random(n, obs_update="full", **kw)
+        auto_says = "in place" if VecTilerSliderEnv.in_place_pays(inplace._obs.numel() * 4, n, T) else "full"
+        ring = []
+        for i in range(16):
+            a = torch.empty(n, dtype=torch.uint8, device=dev)
+            _cabi.check(L.ts_fill_actions(n, ACTION_SEED, 0, i, a.data_ptr(), stream), "ts_fill_actions")
+            ring.append(a)
+        inplace.reset(), full.reset()
+        for i in range(20):
+            inplace.step_async(ring[i & 15]), full.step_async(ring[i & 15])
+        same = torch.equal(inplace._obs, full._obs) and torch.equal(inplace._flags, full._flags) and torch.equal(inplace.positions, full.positions)
+        if not same:
+            say(f"{name}: the two environments DIFFER after 20 steps - not timed")
+            continue
+        t_w = time.perf_counter()  # clocks up before the first round
+        while (time.perf_counter() - t_w) * 1e3 < args.clock_warmup_ms:
+            for i in range(64):
+                full.step_async(ring[i & 15])
+            torch.cuda.synchronize(dev)
+        us_in, us_full = [], []
+        for _ in range(args.rounds):
+            inplace.reset(), full.reset()
+            us_in.append(timed(inplace, ring))
+            us_full.append(timed(full, ring))
+        m_in, m_full = statistics.median(us_in), statistics.median(us_full)
+        kernel = _cabi.describe_launch(inplace._dims, _cabi.OP_STEP, _cabi.OUT_OBS)["name"]
+        say(f"{name:<16} {n:>9} {inplace._obs.numel() * 4 / 2**20:>8.1f}  {kernel:<29}  {' '.join(f'{u:7.2f}' for u in us_in):<23} "
+            f"{' '.join(f'{u:7.2f}' for u in us_full):<23} {m_in:7.2f} {m_full:7.2f}  {m_full / m_in:8.2f}x         {auto_says}")
+        del inplace, full, ring
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
