@@ -149,6 +149,20 @@ def test_every_binding_lists_the_headers_its_source_includes():
         assert {os.path.join(csrc, h) for h in reached} <= seen, (binding.__name__, sorted(seen))
 
 
+def test_the_mlp_header_is_listed_by_the_libraries_of_the_network_and_by_no_other():
+    """ts_mlp.h marks the policy, train, targets and actor-critic libraries stale (the last three extend the policy binding's
+    list) and none of the step, search, table, rollout and update libraries, which do not include it."""
+    from tiler_slider_amd import (_ac_cabi, _cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi, _targets_cabi, _train_cabi,
+                                  _update_cabi)
+    header = os.path.realpath(os.path.join(os.path.dirname(_cabi.SRC), "ts_mlp.h"))
+    assert os.path.isfile(header)
+    for binding in (_policy_cabi, _train_cabi, _targets_cabi, _ac_cabi):
+        assert header in {os.path.realpath(p) for p in binding.HEADERS}, binding.__name__
+    for binding in (_cabi, _search_cabi, _table_cabi, _rollout_cabi, _update_cabi):
+        assert header not in {os.path.realpath(p) for p in binding.HEADERS}, binding.__name__
+    assert header not in {os.path.realpath(p) for p in _cabi.SHARED_HEADERS}
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from tiler_slider_amd import _cabi
     monkeypatch.setattr(_cabi, "_lib", None)

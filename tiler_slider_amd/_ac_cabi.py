@@ -1,7 +1,8 @@
 """ctypes binding of lib/libtiler_slider_ac.so — the actor-critic network's C-ABI declared in include/tiler_slider_ac.h.
 
 An eighth library beside the step, search, table, rollout, policy, train and targets libraries (all seven are pinned symbol by
-symbol and kernel by kernel, so the actor-critic kernels live in their own).  Same rules as _cabi.py: built through
+symbol and kernel by kernel, so the actor-critic kernels live in their own; the network they share with the policy and train
+libraries, value head included, is csrc/ts_mlp.h, listed through _train_cabi.HEADERS).  Same rules as _cabi.py: built through
 _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is
 missing or does not load, every entry point raises.
 """

@@ -2,6 +2,8 @@
 
 A fifth library beside libtiler_slider_hip.so, libtiler_slider_search.so, libtiler_slider_table.so and
 libtiler_slider_rollout.so (all four are pinned symbol by symbol and kernel by kernel, so the policy kernels live in their own).
+The network's device functions and block plans are csrc/ts_mlp.h's, shared with the train and actor-critic libraries: HEADERS
+lists it, so editing it marks all of them (and the targets library, which extends the same list) stale.
 Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there
 is no CPU fallback: if the library is missing or does not load, every entry point raises.
 """
@@ -12,8 +14,9 @@ from . import _cabi
 from ._cabi import Desc, Dims, State
 
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_policy.hip")
-HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in
-                                                  ("tiler_slider_search.h", "tiler_slider_table.h", "tiler_slider_rollout.h", "tiler_slider_policy.h")]
+# ts_mlp.h: the network that ts_policy.hip, ts_train.hip and ts_ac.hip share (_train_cabi, _targets_cabi and _ac_cabi extend this list)
+HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi._PKG, "csrc", "ts_mlp.h")] + [
+    os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h", "tiler_slider_rollout.h", "tiler_slider_policy.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_policy.so")
 
 ABI_VERSION = 1

@@ -1,7 +1,8 @@
 """ctypes binding of lib/libtiler_slider_train.so — the trainable policies' C-ABI declared in include/tiler_slider_train.h.
 
 A sixth library beside the step, search, table, rollout and policy libraries (all five are pinned symbol by symbol and kernel by
-kernel, so the training kernels live in their own).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc
+kernel, so the training kernels live in their own; the network they share with the policy library is csrc/ts_mlp.h, which
+_policy_cabi.HEADERS lists).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc
 --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is missing or does not load,
 every entry point raises.
 """

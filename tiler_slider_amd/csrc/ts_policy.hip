@@ -24,17 +24,16 @@
 //     laid out [j][slot]: lanes on different cells read different banks, lanes on equal cells are a broadcast.  Where they do not
 //     fit beside hs in the 64 KiB a block may ask for (ts_launch.h), they are gathered from global memory instead - a decision
 //     of plan(), not a limit.
+//
+// The network - stage_weights, static_preact, logits_of - and the block plan are ts_mlp.h's, shared with ts_train.hip and
+// ts_ac.hip.
 #include "../../include/tiler_slider_policy.h"
-#include "ts_launch.h"
+#include "ts_mlp.h"
 
 namespace {
 
-using ts::kWave;
-constexpr int kMaxThreads = 256;  // at most four waves per block; waves interact only through the staged weights
-constexpr int kMaxTargets = TS_ROLLOUT_MAX_TILES;
-constexpr int kMaxTilesLane = TS_ROLLOUT_MAX_TILES;
-
 struct PArgs {
+  static constexpr bool kValue = false;  // no value head
   uint8_t *pos;  // cell_t = uint8 (S <= 8)
   const uint8_t *init, *tgt;
   const uint32_t *blk;
@@ -49,109 +48,6 @@ struct PArgs {
   int32_t T, Tt, mc, max_steps, steps, autoreset, write_state;
   int32_t H, slots, staged, wt_floats;  // slots: T' * S*S; wt_floats: LDS floats of the staged tile-plane weights
 };
-
-template <int S>
-constexpr int max_tiles() {
-  return S * S < kMaxTilesLane ? S * S : kMaxTilesLane;
-}
-
-// hs, the static pre-activations of a lane's board: the lane's column of [j][thread] in LDS
-struct Hs {
-  float *p;
-  int stride;
-  __device__ __forceinline__ Hs(float *base, int threads) : p(base), stride(threads) {}
-  __device__ __forceinline__ float &at(int j) { return p[j * stride]; }
-};
-constexpr int kHsLdsBytesPerUnit = 4;
-
-// LDS of a block: [w2 [H][4] | b2 [4]] [w1t [H][slots], where staged, rounded up to 16 bytes] [hs [H][threads]]
-__host__ __device__ constexpr int head_floats(int H) { return 4 * H + 4; }
-
-extern __shared__ float g_lds[];
-
-// the second layer, and the tile-plane rows of w1 (features C .. C + slots - 1) transposed into [j][slot]; global reads are contiguous
-__device__ __forceinline__ void stage_weights(const PArgs &a, int C) {
-  const int nh = 4 * a.H;
-  for (int i = threadIdx.x; i < nh; i += blockDim.x) g_lds[i] = a.w2[i];
-  if (threadIdx.x < 4) g_lds[nh + threadIdx.x] = a.b2[threadIdx.x];
-  if (a.staged) {
-    float *wt = g_lds + head_floats(a.H);
-    const int total = a.H * a.slots;
-    const float *src = a.w1 + (int64_t)C * a.H;
-    for (int i = threadIdx.x; i < total; i += blockDim.x) {
-      const int slot = i / a.H, j = i - slot * a.H;
-      wt[j * a.slots + slot] = src[i];
-    }
-  }
-  __syncthreads();
-}
-
-// the prologue: everything of the first layer that a rollout cannot change
-template <int S, class M>
-__device__ __forceinline__ void static_preact(const PArgs &a, Hs &hs, M blk, M tgm, const uint32_t (&tg)[kMaxTargets]) {
-  constexpr int C = S * S;
-  const int H = a.H;
-  for (int j = 0; j < H; ++j) hs.at(j) = a.b1[j];
-  // one feature per lane and round: the lowest bit left of the lane's mask, until no lane of the wave has one
-  auto add_bits = [&](M m, int plane) {
-    while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
-      const bool has = m != 0;
-      const int p = has ? ts::lsb(m) : 0;
-      m &= m - 1;
-      const float *row = a.w1 + (int64_t)(plane * C + p) * H;
-      for (int j = 0; j < H; ++j) hs.at(j) += has ? row[j] : 0.0f;
-    }
-  };
-  add_bits(blk, 0);
-  if (a.mc) {
-#pragma unroll
-    for (int t = 0; t < kMaxTargets; ++t) {
-      if (t < a.Tt) {
-        const float *row = a.w1 + (int64_t)((1 + a.T + t) * C + (int)tg[t]) * H;
-        for (int j = 0; j < H; ++j) hs.at(j) += row[j];
-      }
-    }
-  } else {
-    add_bits(tgm, 2);
-  }
-}
-
-// the logits of the board whose clamped cells are pc[]
-template <int S, int MT>
-__device__ __forceinline__ void logits_of(const PArgs &a, Hs &hs, const uint32_t (&pc)[MT], float (&z)[4]) {
-  using M = typename ts::Bitboard<S>::mask_t;
-  constexpr int C = S * S;
-  const int H = a.H, T = a.T;
-  uint32_t slot[MT];
-  bool inc[MT];  // single colour: a cell counts once
-  M seen = 0;
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    slot[t] = a.mc ? (uint32_t)(t * C) + pc[t] : pc[t];
-    inc[t] = a.mc || !((seen >> pc[t]) & 1);
-    if (t < T) seen |= M(1) << pc[t];
-  }
-  const float4 *w2 = reinterpret_cast<const float4 *>(g_lds);
-  const float4 b2 = w2[H];
-  z[0] = b2.x, z[1] = b2.y, z[2] = b2.z, z[3] = b2.w;
-  const float *tile_rows = a.w1 + (int64_t)C * H;
-  for (int j = 0; j < H; ++j) {
-    float acc = hs.at(j);
-    if (a.staged) {
-      const float *row = g_lds + head_floats(H) + j * a.slots;
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-        if (t < T) acc += inc[t] ? row[slot[t]] : 0.0f;
-    } else {
-#pragma unroll
-      for (int t = 0; t < MT; ++t)
-        if (t < T) acc += inc[t] ? tile_rows[(int64_t)slot[t] * H + j] : 0.0f;
-    }
-    const float h = fmaxf(acc, 0.0f);
-    const float4 w = w2[j];  // one address for the whole wave: a broadcast
-    z[0] = fmaf(h, w.x, z[0]), z[1] = fmaf(h, w.y, z[1]), z[2] = fmaf(h, w.z, z[2]), z[3] = fmaf(h, w.w, z[3]);
-  }
-}
 
 // e of the definition; <= 3 whatever z holds
 template <int SELECT>
@@ -176,6 +72,7 @@ struct Board {
 };
 
 // the board of lane nl: obstacles, targets, cells as they lie in memory, and (auto-reset) the clamped initial cells
+// (the obstacle and target part is ts_mlp.h's load_level, written out: calling it changed 23 of the 24 kernels here)
 template <int S>
 __device__ __forceinline__ void load_board(const PArgs &a, int64_t nl, bool want_init, Board<S> &b) {
   using M = typename Board<S>::M;
@@ -221,7 +118,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_policy_logits(const PArgs a) {
   const int64_t nl = live ? n : N - 1;
   Board<S> b;
   load_board<S>(a, nl, false, b);
-  Hs hs(g_lds + head_floats(a.H) + a.wt_floats + threadIdx.x, (int)blockDim.x);
+  Hs hs(g_lds + head_floats<PArgs::kValue>(a.H) + a.wt_floats + threadIdx.x, (int)blockDim.x);
   static_preact<S>(a, hs, b.blk, b.tgm, b.tg);
   uint32_t pc[MT];
 #pragma unroll
@@ -258,7 +155,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_policy_rollout(const PArgs a) {
   const uint64_t draw = (uint64_t)(a.board_offset + nl) * ts::kDrawMul;
 
   // ---- the network's constant part, once ----
-  Hs hs(g_lds + head_floats(a.H) + a.wt_floats + threadIdx.x, (int)blockDim.x);
+  Hs hs(g_lds + head_floats<PArgs::kValue>(a.H) + a.wt_floats + threadIdx.x, (int)blockDim.x);
   static_preact<S>(a, hs, blk, tgm, tg);
 
   // build-defined Manhattan reward of the cells c[] (include/tiler_slider.h: ts_reward)
@@ -430,45 +327,16 @@ Kernel logits_kernel(int S) {
 bool valid_select(int32_t s) { return s == TS_POLICY_GREEDY || s == TS_POLICY_SAMPLE; }
 
 // valid dims: the random rollout's shapes (a board's dynamic and static state stays in registers), every allowed width
-bool shape_supported(const ts_dims *d, int32_t hidden) {
-  return d->size <= TS_ROLLOUT_MAX_SIZE && d->n_tiles <= TS_ROLLOUT_MAX_TILES && d->n_targets <= TS_ROLLOUT_MAX_TILES && hidden >= 1 &&
-         hidden <= TS_POLICY_MAX_HIDDEN;
-}
+using PolicyPlan = Plan<PArgs, ts_policy_desc>;
 
-struct Plan {
-  Kernel kernel = nullptr;
-  uint32_t blocks = 0, threads = 0;
-  size_t lds = 0;
-  int32_t slots = 0, staged = 0, wt_floats = 0;
-  ts_policy_desc desc{};
-};
-
-// The block of a supported shape: the most waves (four, two, one) whose hs columns leave room, behind the second layer, for the
-// tile-plane weights in the LDS a block may ask for; where not even one wave's do, the weights stay in global memory.
-void plan_block(const ts_dims *d, int32_t H, Plan &p) {
-  const int C = d->size * d->size;
-  p.slots = (d->multi_color ? d->n_tiles : 1) * C;
-  const size_t wt_bytes = d->n_tiles > 0 ? ((size_t)H * p.slots * 4u + 15u) & ~(size_t)15u : 0u;
-  const size_t hs_bytes = (size_t)H * kHsLdsBytesPerUnit;  // per thread
-  const size_t head_bytes = (size_t)head_floats(H) * 4u;   // w2 and b2, always staged
-  p.threads = 0;
-  for (const uint32_t threads : {256u, 128u, 64u}) {
-    if (wt_bytes > 0 && head_bytes + wt_bytes + hs_bytes * threads <= ts::kMaxBlockLds) {
-      p.threads = threads, p.staged = 1, p.wt_floats = (int32_t)(wt_bytes / 4u);
-      break;
-    }
-  }
-  if (!p.threads) {
-    p.staged = 0, p.wt_floats = 0;
-    p.threads = head_bytes + hs_bytes * 256u <= ts::kMaxBlockLds ? 256u : head_bytes + hs_bytes * 128u <= ts::kMaxBlockLds ? 128u : 64u;
-  }
-  p.lds = head_bytes + (size_t)p.wt_floats * 4u + hs_bytes * p.threads;
+void plan_block(const ts_dims *d, int32_t H, PolicyPlan &p) {
+  plan_forward_block(d, H, p);
   p.desc.threads_per_block = (int32_t)p.threads;
   p.desc.lds_bytes = (int32_t)p.lds;
   p.desc.weights_in_lds = p.staged;
 }
 
-int32_t plan_grid(const ts_dims *d, Plan &p) {
+int32_t plan_grid(const ts_dims *d, PolicyPlan &p) {
   const int64_t blocks = (d->n_boards + p.threads - 1) / p.threads;
   if (!p.kernel || blocks > 0x7fffffffll) return TS_ERR_LIMIT;
   p.blocks = (uint32_t)blocks;
@@ -477,7 +345,7 @@ int32_t plan_grid(const ts_dims *d, Plan &p) {
 }
 
 // Every check of ts_policy_rollout that needs no pointer of st / mlp's parameters / out, and the launch it would make
-int32_t plan_rollout(const ts_dims *d, int32_t hidden, const ts_policy_cfg *cfg, uint32_t out_mask, Plan &p) {
+int32_t plan_rollout(const ts_dims *d, int32_t hidden, const ts_policy_cfg *cfg, uint32_t out_mask, PolicyPlan &p) {
   if (const int32_t rc = ts::check_dims(d); rc != TS_OK) return rc;
   if (!cfg) return TS_ERR_NULL;
   if (!shape_supported(d, hidden)) return TS_ERR_LIMIT;
@@ -495,7 +363,7 @@ int32_t plan_rollout(const ts_dims *d, int32_t hidden, const ts_policy_cfg *cfg,
   return TS_OK;
 }
 
-int32_t plan_logits(const ts_dims *d, int32_t hidden, Plan &p) {
+int32_t plan_logits(const ts_dims *d, int32_t hidden, PolicyPlan &p) {
   if (const int32_t rc = ts::check_dims(d); rc != TS_OK) return rc;
   if (!shape_supported(d, hidden)) return TS_ERR_LIMIT;
   plan_block(d, hidden, p);
@@ -507,7 +375,7 @@ int32_t plan_logits(const ts_dims *d, int32_t hidden, Plan &p) {
   return TS_OK;
 }
 
-void fill_common(PArgs &a, const ts_dims *dims, const ts_state *st, const ts_mlp *mlp, const Plan &p) {
+void fill_common(PArgs &a, const ts_dims *dims, const ts_state *st, const ts_mlp *mlp, const PolicyPlan &p) {
   a.pos = static_cast<uint8_t *>(st->pos), a.init = static_cast<const uint8_t *>(st->init), a.tgt = static_cast<const uint8_t *>(st->tgt);
   a.blk = st->blk, a.step_count = st->step_count, a.done = st->done;
   a.w1 = mlp->w1, a.b1 = mlp->b1, a.w2 = mlp->w2, a.b2 = mlp->b2;
@@ -516,7 +384,6 @@ void fill_common(PArgs &a, const ts_dims *dims, const ts_state *st, const ts_mlp
   a.H = mlp->hidden, a.slots = p.slots, a.staged = p.staged, a.wt_floats = p.wt_floats;
 }
 
-bool mlp_complete(const ts_mlp *mlp) { return mlp->w1 && mlp->b1 && mlp->w2 && mlp->b2; }
 
 }  // namespace
 
@@ -525,16 +392,11 @@ extern "C" {
 int32_t ts_policy_abi_version(void) { return TS_POLICY_ABI_VERSION; }
 int32_t ts_policy_last_hip_error(void) { return ts::t_last_hip_error; }
 
-int32_t ts_policy_supported(const ts_dims *dims, int32_t hidden) {
-  const int32_t rc = ts::check_dims(dims);
-  if (rc == TS_ERR_LIMIT) return 0;
-  if (rc != TS_OK) return rc;
-  return shape_supported(dims, hidden) ? 1 : 0;
-}
+int32_t ts_policy_supported(const ts_dims *dims, int32_t hidden) { return supported(dims, hidden); }
 
 int32_t ts_describe_policy_rollout(const ts_dims *dims, int32_t hidden, const ts_policy_cfg *cfg, uint32_t out_mask, ts_policy_desc *desc) {
   if (!dims || !cfg || !desc) return TS_ERR_NULL;
-  Plan p;
+  PolicyPlan p;
   const int32_t rc = plan_rollout(dims, hidden, cfg, out_mask, p);
   if (rc != TS_OK) return rc;
   *desc = p.desc;
@@ -543,7 +405,7 @@ int32_t ts_describe_policy_rollout(const ts_dims *dims, int32_t hidden, const ts
 
 int32_t ts_describe_policy_logits(const ts_dims *dims, int32_t hidden, ts_policy_desc *desc) {
   if (!dims || !desc) return TS_ERR_NULL;
-  Plan p;
+  PolicyPlan p;
   const int32_t rc = plan_logits(dims, hidden, p);
   if (rc != TS_OK) return rc;
   *desc = p.desc;
@@ -553,7 +415,7 @@ int32_t ts_describe_policy_logits(const ts_dims *dims, int32_t hidden, ts_policy
 int32_t ts_policy_logits(const ts_dims *dims, const ts_state *st, const ts_mlp *mlp, float *logits, void *stream) {
   if (const int32_t rc = ts::check_dims(dims); rc != TS_OK) return rc;
   if (!mlp) return TS_ERR_NULL;
-  Plan p;
+  PolicyPlan p;
   if (const int32_t rc = plan_logits(dims, mlp->hidden, p); rc != TS_OK) return rc;
   if (!p.kernel) return TS_OK;  // an empty batch
   if (!st || !logits || !mlp_complete(mlp) || !st->blk || (dims->n_tiles > 0 && !st->pos) || (dims->n_targets > 0 && !st->tgt)) return TS_ERR_NULL;
@@ -575,7 +437,7 @@ int32_t ts_policy_rollout(const ts_dims *dims, const ts_state *st, const ts_mlp 
                                    (out->reward_sum ? TS_ROLLOUT_OUT_REWARD_SUM : 0u) | (out->flags ? TS_ROLLOUT_OUT_FLAGS : 0u) |
                                    (out->act_log ? TS_ROLLOUT_OUT_ACT_LOG : 0u) | (out->flags_log ? TS_ROLLOUT_OUT_FLAGS_LOG : 0u) |
                                    (out->pos_log ? TS_ROLLOUT_OUT_POS_LOG : 0u) | (out->logits_log ? TS_POLICY_OUT_LOGITS_LOG : 0u);
-  Plan p;
+  PolicyPlan p;
   if (const int32_t rc = plan_rollout(dims, mlp->hidden, cfg, mask, p); rc != TS_OK) return rc;
   if (!p.kernel) return TS_OK;  // an empty batch or no step: nothing to launch, no pointer is looked at
   const bool autoreset = (cfg->mode & TS_MODE_AUTORESET) != 0;
