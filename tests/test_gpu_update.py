@@ -9,12 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import table_harness as th
+import update_cases as cases
+from update_cases import ACTION_SEED, AUTORESET, LEVEL_SEED, SUCCESS, TIMEOUT, VOID
+
 pytestmark = pytest.mark.gpu
 
-LEVEL_SEED = 0x715311DE
-ACTION_SEED = 0xAC710005
 STEPS = 24
-VOID = 0x10 | 0x20 | 0x40  # STEPPED_DONE | AUTORESET | BAD_ACTION: no transition was played
 
 # name: (S, T, Tt, obstacles, multi colour, max_steps, boards); ragged batches: 322 = 5 waves + 2 boards, 331 = 5 waves + 11
 CASES = {
@@ -100,11 +101,17 @@ class _Raw:
         self.obs = self.whole[guard:guard + self.N * S * S * 3].view(self.N, S, S, 3)
         self.shown = torch.full_like(self.pos, 0xDD)
         self.dims = _cabi.Dims(self.N, S, T, Tt, int(mc), max_steps, 0)
-        self.state = _cabi.State(self.pos.data_ptr(), self.init.data_ptr(), self.tgt.data_ptr() if Tt else None, self.blk.data_ptr(),
-                                 self.step_count.data_ptr(), self.done.data_ptr(), None)
-        self.out = _cabi.StepOut(self.flags.data_ptr(), None if u8 else self.obs.data_ptr(), self.reward.data_ptr(), None, None,
-                                 self.obs.data_ptr() if u8 else None, None)
         self.stream = torch.cuda.current_stream(dev).cuda_stream
+        self.bind()
+
+    def bind(self):
+        """The C structs of the tensors as they are now (again after a tensor was replaced: tensors held between guard bytes,
+        an observation at an odd address)."""
+        from tiler_slider_amd import _cabi
+        self.state = _cabi.State(self.pos.data_ptr(), self.init.data_ptr(), self.tgt.data_ptr() if self.dims.n_targets else None,
+                                 self.blk.data_ptr(), self.step_count.data_ptr(), self.done.data_ptr(), None)
+        self.out = _cabi.StepOut(self.flags.data_ptr(), None if self.u8 else self.obs.data_ptr(), self.reward.data_ptr(), None, None,
+                                 self.obs.data_ptr() if self.u8 else None, None)
 
     def encode(self, into=None):
         """ts_encode / ts_encode_u8 of the current cells into the observation (or `into`)."""
@@ -359,3 +366,307 @@ def test_forced_in_place_environment_and_captured_graphs(torch_cuda, oracle):
         twin.step_async(acts[0]), twin.step_async(acts[1])
         torch.cuda.synchronize()
         assert torch.equal(fresh._obs, twin._obs) and torch.equal(fresh.positions, twin.positions), dtype
+
+
+# ---- every compiled kernel (tests/update_cases.py: one entry per kernel of the code object) ----
+_FIELDS = ("pos", "step_count", "done", "flags", "reward", "obs")
+_LABELS = [f"{f} vs {ref}" for f in _FIELDS for ref in ("ts_step", "oracle")] + ["shown == pos"]
+
+
+def _oracle_run(oracle, S, mc, max_steps, lv, mode, steps, obs=True):
+    """`steps` steps of the oracle on the levels `lv` under _actions' stream (unpatched below 63 boards, where the two bad
+    bytes a step would be most of the batch): per step the actions and everything a step writes."""
+    ref = oracle.OracleBatch(S, mc, max_steps, *lv)
+    ref.reset()
+    out = []
+    for k in range(steps):
+        act = _actions(oracle, ref.n, k) if ref.n >= 63 else oracle.fill_actions(ref.n, seed=ACTION_SEED, step_index=k)
+        want = ref.step(act, mode=mode, reward=True, obs=obs)
+        row = dict(act=act, flags=want["flags"], reward=want["reward"], pos=ref.pos.copy(), step_count=ref.step_count.copy(), done=ref.done.copy())
+        if obs:
+            row["obs"] = want["obs"]
+        out.append(row)
+    return out
+
+
+def _upload(torch, run):
+    return [{f: torch.from_numpy(v).cuda() for f, v in row.items()} for row in run]
+
+
+def _compare_run(torch, a, b, want, mode):
+    """Steps `a` through ts_step and `b` through ts_step_update over the oracle's run `want` (device tensors).  After every step
+    the six fields of b against a's and against the oracle's (where the run holds them), and shown == pos; the verdicts stay on
+    the device until the run is over.  Returns the failures as (step, what), first step first."""
+    rows = []
+    yes = torch.ones((), dtype=torch.bool, device="cuda")
+    for w in want:
+        a.step(w["act"], mode)
+        b.step_update(w["act"], mode)
+        fa, fb = a.fields(), b.fields()
+        row = []
+        for f in _FIELDS:
+            row.append((fa[f] == fb[f]).all())
+            row.append((fb[f] == w[f]).all() if f in w else yes)
+        row.append((b.shown == b.pos).all())
+        rows.append(torch.stack(row))
+    ok = torch.stack(rows).cpu().numpy()
+    return [(k, _LABELS[j]) for k, j in np.argwhere(~ok).tolist()]
+
+
+def _launches(raw, name):
+    """The kernel ts_step_update launches for this copy's dims and outputs is the case's."""
+    from tiler_slider_amd import _cabi, _update_cabi
+    outputs = (_cabi.OUT_OBS_U8 if raw.u8 else _cabi.OUT_OBS) | _cabi.OUT_REWARD
+    return _update_cabi.describe_step_update(raw.dims, outputs)["name"] == name
+
+
+_CASE_RUNS = {}  # of the shape run last, as _OCC_RUN below
+
+
+def _case_run(oracle, name, mc, mode):
+    """Levels and the oracle's 24 steps of a case's shape in a ragged batch of 331, once for both observation types."""
+    key = (cases.shape_key(name), mc, mode)
+    if key not in _CASE_RUNS:
+        if any(k[0] != key[0] for k in _CASE_RUNS):
+            _CASE_RUNS.clear()
+        lv = cases.levels(oracle, name, 331, mc)
+        _CASE_RUNS[key] = (lv, _oracle_run(oracle, cases.CASES[name][0], mc, 6, lv, mode, STEPS))
+    return _CASE_RUNS[key]
+
+
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_every_update_kernel_in_a_ragged_batch(torch_cuda, oracle, name):
+    """One case per kernel of the code object (tests/update_cases.py; tests/test_update_cpu.py pins the table to it): 331
+    boards - five waves and eleven lanes - both colour modes, both step modes, 24 steps with max_steps 6 and a few bad action
+    bytes.  After every step pos, step_count, done, flags, reward and the observation equal ts_step's and the oracle's, and
+    shown == pos.  The oracle's flags of the autoreset runs keep the table's floors: tiles move, boards win, time out and are
+    reset."""
+    torch = torch_cuda
+    S, T, Tt, K = cases.CASES[name]
+    u8 = cases.is_u8(name)
+    failures = []
+    for mc in (True, False):
+        for mode in (oracle.MODE_STRICT, oracle.MODE_AUTORESET):
+            lv, run = _case_run(oracle, name, mc, mode)
+            a = _Raw(torch, S, T, Tt, mc, 6, *lv, u8)
+            b = _Raw(torch, S, T, Tt, mc, 6, *lv, u8)
+            assert _launches(b, name) and (Tt > 0 or b.state.tgt is None)
+            b.show()
+            bad = _compare_run(torch, a, b, _upload(torch, run), mode)
+            failures += [("multi" if mc else "single", "autoreset" if mode else "strict") + x for x in bad[:6]]
+            flags = np.stack([row["flags"] for row in run])
+            print(f"{name} {'multi' if mc else 'single'} colour, mode {mode}: moved {cases.stats(flags)[0]:.2f}, wins / autoresets / timeouts {cases.stats(flags)[1:]}")
+            if mode == oracle.MODE_AUTORESET:
+                cases.assert_floors(name, mc, flags)
+    assert not failures, (name, failures)
+
+
+OCC_BOARDS, OCC_STEPS = 262_144, 8
+_OCC_RUN = {}  # the shape run last: a kernel's two observation types follow each other in sorted(CASES)
+
+
+def _occupancy_run(oracle, name):
+    key = cases.shape_key(name)
+    if key not in _OCC_RUN:
+        _OCC_RUN.clear()
+        S = key[0]
+        lv = cases.levels(oracle, name, OCC_BOARDS, S % 2 == 0)
+        _OCC_RUN[key] = (lv, _oracle_run(oracle, S, S % 2 == 0, 5, lv, oracle.MODE_AUTORESET, OCC_STEPS, obs=False))
+    return _OCC_RUN[key]
+
+
+@pytest.mark.parametrize("name", sorted(cases.CASES))
+def test_every_update_kernel_at_occupancy(torch_cuda, oracle, name):
+    """The same table at 262,144 distinct boards - 4,096 waves, 16 per CU: multi colour on even sizes, single colour on odd
+    ones, autoreset mode, max_steps 5, 8 steps.  After every step all six fields equal a ts_step twin's and shown == pos; pos,
+    step_count, done, flags and reward equal the oracle's; after the last step the observation is ts_encode of the final state.
+    By the oracle's flags the run holds autoresets, and wins exactly where the counts allow them."""
+    torch = torch_cuda
+    S, T, Tt, K = cases.CASES[name]
+    u8, mc = cases.is_u8(name), S % 2 == 0
+    lv, run = _occupancy_run(oracle, name)
+    a = _Raw(torch, S, T, Tt, mc, 5, *lv, u8)
+    b = _Raw(torch, S, T, Tt, mc, 5, *lv, u8)
+    assert _launches(b, name) and b.N == OCC_BOARDS
+    b.show()
+    bad = _compare_run(torch, a, b, _upload(torch, run), oracle.MODE_AUTORESET)
+    assert not bad, (name, bad[:8])
+    full = torch.empty_like(b.obs)
+    b.encode(into=full)
+    assert torch.equal(b.obs, full), (name, "the observation against ts_encode of the final state")
+    moved, wins, resets, timeouts = cases.stats(np.stack([row["flags"] for row in run]))
+    print(f"{name}: moved {moved:.2f}, {wins} wins, {resets} autoresets, {timeouts} timeouts")
+    assert resets >= OCC_BOARDS and (timeouts > 0 or not cases.can_move(name)), (name, resets, timeouts)  # step 5 times out, step 6 resets
+    expected = cases.wins_expected(name, mc)
+    assert expected is None or (wins >= 1000 if expected else wins == 0), (name, wins)
+    assert (moved >= 0.2) if cases.can_move(name) else moved == 0, (name, moved)
+
+
+def _between_guards(torch, raw):
+    """Every buffer of `raw` that ts_step_update reads or writes moves into an allocation of its own between table_harness's
+    guard bytes.  Returns {field: (guarded buffer, the payload's bytes as they are now)}."""
+    held = {}
+    for f in ("pos", "shown", "step_count", "done", "flags", "reward", "obs", "init", "tgt", "blk"):
+        t = getattr(raw, f)
+        if t.numel() == 0:
+            continue
+        before = t.cpu().numpy()
+        g = th.guarded(torch, t.device, before)
+        setattr(raw, f, g[th.GUARD:g.numel() - th.GUARD].view(t.dtype).view(t.shape))
+        held[f] = (g, before)
+    raw.whole = held["obs"][0]
+    raw.bind()
+    return held
+
+
+def _edge_batches(torch, oracle):
+    """N = 1 (63 lanes play a copy of the only board and must write nothing), one lane either side of a wave, one lane either
+    side of a block (257: the second block's last three waves leave at the wave-uniform return), on a 32-bit and on a partly
+    filled 64-bit mask: against ts_step and the oracle, every buffer of the in-place copy between guard bytes.  The guard is
+    256 bytes: a stray observation store of the first lane past the batch lands in it at 4x4 (a board is 192 bytes of float32)
+    and at 7x7 in uint8 (147 bytes), not at 7x7 in float32 (588 bytes) - there the state buffers' guards are what bites."""
+    for stem in ("k_step_update<4, 2, ", "k_step_update<7, 8, "):
+        for N in (1, 63, 64, 65, 255, 256, 257):
+            for mc in (True, False):
+                lv = cases.levels(oracle, stem + "false>", N, mc)
+                S, T, Tt, K = cases.CASES[stem + "false>"]
+                for mode in (oracle.MODE_AUTORESET, oracle.MODE_STRICT):
+                    run = _oracle_run(oracle, S, mc, 6, lv, mode, 12)
+                    for u8 in (False, True):
+                        what = (stem, N, mc, mode, u8)
+                        a = _Raw(torch, S, T, Tt, mc, 6, *lv, u8)
+                        b = _Raw(torch, S, T, Tt, mc, 6, *lv, u8)
+                        assert _launches(b, stem + ("true>" if u8 else "false>"))
+                        b.show()
+                        held = _between_guards(torch, b)
+                        want = _upload(torch, run)
+                        acts = [th.guarded(torch, b.pos.device, row["act"]) for row in run]
+                        for w, g in zip(want, acts):
+                            w["act"] = g[th.GUARD:th.GUARD + N]
+                        bad = _compare_run(torch, a, b, want, mode)
+                        assert not bad, (what, bad[:8])
+                        for f, (g, before) in held.items():
+                            try:
+                                now = th.payload(g, before.dtype, before.shape)  # asserts the guard bytes
+                            except AssertionError as e:
+                                raise AssertionError((what, f, str(e))) from None
+                            if f in ("init", "tgt", "blk"):
+                                assert np.array_equal(now, before), (what, f, "an input was written")
+                            else:
+                                assert np.array_equal(now, getattr(a, "pos" if f == "shown" else f).cpu().numpy()), (what, f)
+                        for row, g in zip(run, acts):
+                            try:
+                                assert np.array_equal(th.payload(g, np.uint8, (N,)), row["act"]), "actions were written"
+                            except AssertionError as e:
+                                raise AssertionError((what, "actions", str(e))) from None
+
+
+def _edge_odd_address(torch, oracle):
+    """The header asks no alignment of a uint8 observation: the in-place copy's starts 1 and 3 bytes into its allocation (the
+    ts_step twin and ts_encode_u8 keep aligned ones).  Contents equal the twin's after every step; no byte outside the view
+    changes."""
+    N = 331
+    for name in ("k_step_update<5, 8, true>", "k_step_update<6, 8, true>"):
+        S, T, Tt, K = cases.CASES[name]
+        mc = S % 2 == 0
+        lv = cases.levels(oracle, name, N, mc)
+        want = _upload(torch, _oracle_run(oracle, S, mc, 6, lv, oracle.MODE_AUTORESET, 8))
+        for off in (1, 3):
+            a = _Raw(torch, S, T, Tt, mc, 6, *lv, True)
+            b = _Raw(torch, S, T, Tt, mc, 6, *lv, True)
+            n = b.obs.numel()
+            b.whole = torch.full((n + 8,), 99, dtype=torch.uint8, device="cuda")
+            b.obs = b.whole[off:off + n].view(N, S, S, 3)
+            b.bind()
+            assert b.obs.data_ptr() % 4 == off and a.obs.data_ptr() % 4 == 0 and _launches(b, name)
+            b.obs.copy_(a.encode())  # the contract on entry: the full encoding, written by other means
+            b.shown.copy_(b.pos)
+            bad = _compare_run(torch, a, b, want, oracle.MODE_AUTORESET)
+            assert not bad, (name, off, bad[:8])
+            full = torch.empty_like(a.obs)
+            b.encode(into=full)
+            assert torch.equal(b.obs, full), (name, off, "ts_encode_u8 of the final state")
+            assert bool((b.whole[:off] == 99).all()) and bool((b.whole[off + n:] == 99).all()), (name, off, "bytes around the view")
+
+
+def _edge_max_steps_1(torch, oracle):
+    """max_steps = 1: every played step times out, in autoreset mode every other step is the reset.  On the one-cell board the
+    same step carries IS_WON | SUCCESS | TIMEOUT; 6x6 with two tiles."""
+    N = 331
+    for stem in ("k_step_update<1, 2, ", "k_step_update<6, 2, "):
+        S, T, Tt, K = cases.CASES[stem + "false>"]
+        for mc in (True, False):
+            lv = cases.levels(oracle, stem + "false>", N, mc)
+            for mode in (oracle.MODE_AUTORESET, oracle.MODE_STRICT):
+                run = _oracle_run(oracle, S, mc, 1, lv, mode, 8)
+                flags = np.stack([row["flags"] for row in run])
+                played = (flags & VOID) == 0
+                assert ((flags[played] & TIMEOUT) != 0).all() and played[0].sum() >= N - 2
+                if mode == oracle.MODE_AUTORESET:
+                    assert int(((flags & AUTORESET) != 0).sum()) >= 4 * (N - 8) and int(played.sum()) >= 4 * (N - 8)
+                if S == 1:
+                    won_in_time = cases.IS_WON | SUCCESS | TIMEOUT
+                    assert ((flags[played] & won_in_time) == won_in_time).all()
+                for u8 in (False, True):
+                    a = _Raw(torch, S, T, Tt, mc, 1, *lv, u8)
+                    b = _Raw(torch, S, T, Tt, mc, 1, *lv, u8)
+                    assert _launches(b, stem + ("true>" if u8 else "false>"))
+                    b.show()
+                    bad = _compare_run(torch, a, b, _upload(torch, run), mode)
+                    assert not bad, (stem, mc, mode, u8, bad[:8])
+
+
+@pytest.mark.parametrize("edge", ("batches", "odd_address", "max_steps_1"))
+def test_edges_of_the_launch_and_the_buffers(torch_cuda, oracle, edge):
+    """Small and boundary batches with every buffer between guard bytes; a uint8 observation at an odd address; max_steps 1."""
+    {"batches": _edge_batches, "odd_address": _edge_odd_address, "max_steps_1": _edge_max_steps_1}[edge](torch_cuda, oracle)
+
+
+def test_forced_in_place_environment_on_a_64_bit_mask(torch_cuda, oracle):
+    """obs_update="inplace" on 7x7 boards (49 of the mask's 64 bits) with 3 tiles and 5 obstacles, 4,099 boards of the case
+    table's winnable construction, float32 single colour and uint8 multi colour with reward, against an obs_update="full" twin:
+    reset(), a captured graph of four steps replayed twice, rollout(3, "random"), four eager steps - observation, flags,
+    positions and step_count equal throughout, boards win on the way, and at the end _shown == positions."""
+    torch = torch_cuda
+    from tiler_slider_amd import VecTilerSliderEnv, _cabi
+    N = 4099
+    acts = [torch.from_numpy(_actions(oracle, N, k)).cuda() for k in range(8)]
+    for dtype, mc in (("float32", False), ("uint8", True)):
+        blk, init, tgt = cases.make_levels(oracle, 7, 3, 3, 5, N, mc)
+        kw = dict(multi_color=mc, max_steps=7, auto_reset=True, obs_dtype=dtype, with_reward=dtype == "uint8")
+        env = VecTilerSliderEnv.from_arrays(7, blk, init, tgt, obs_update="inplace", **kw)
+        full = VecTilerSliderEnv.from_arrays(7, blk, init, tgt, obs_update="full", **kw)
+        outputs = (_cabi.OUT_OBS if dtype == "float32" else _cabi.OUT_OBS_U8 | _cabi.OUT_REWARD)
+        assert env._in_place and not full._in_place
+        assert _cabi.describe_launch(env._dims, _cabi.OP_STEP, outputs)["name"] == f"k_step_update<7, 8, {'false' if dtype == 'float32' else 'true'}>"
+
+        def same(what):
+            assert torch.equal(env._obs, full._obs), (dtype, what, "obs")
+            assert torch.equal(env._flags, full._flags), (dtype, what, "flags")
+            assert torch.equal(env.positions, full.positions) and torch.equal(env.step_count, full.step_count), (dtype, what, "state")
+            if dtype == "uint8":
+                assert torch.equal(env._reward, full._reward), (dtype, what, "reward")
+
+        assert torch.equal(env.reset(), full.reset())
+        wins = 0
+        graph = env.capture_steps(acts[:4])
+        for rep in range(2):
+            graph.replay()
+            for k in range(4):
+                full.step_async(acts[k])
+                wins += int(((full._flags & SUCCESS) != 0).sum())
+            torch.cuda.synchronize()
+            same(("replay", rep))
+            assert torch.equal(env._shown, env.positions)
+        env.rollout(3, "random", seed=5)
+        full.rollout(3, "random", seed=5)
+        same("rollout")  # the rollout re-encodes the observation, rebinds the flags and re-synchronises _shown
+        assert torch.equal(env._shown, env.positions), (dtype, "rollout", "shown")
+        for k in range(4, 8):
+            obs, done, info = env.step(acts[k])
+            fobs, fdone, finfo = full.step(acts[k])
+            assert torch.equal(obs, fobs) and torch.equal(done, fdone) and torch.equal(info["flags"], finfo["flags"]), (dtype, k)
+            same(("eager", k))
+            wins += int(((finfo["flags"] & SUCCESS) != 0).sum())
+        assert wins >= 100, (dtype, wins)  # half the boards win one step in four
+        assert torch.equal(env._shown, env.positions)

@@ -6,6 +6,9 @@ import re
 import subprocess
 import sys
 
+import pytest
+
+import update_cases as cases
 from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
 from conftest import ROOT
 
@@ -192,6 +195,56 @@ def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_update_library(monkeypa
     assert n_kernels == uc.MIN_KERNELS  # the metadata was found and parsed: exactly the kernels the library holds
     assert class_a == [] and class_b == []
     _assert_build_goes_through_the_guard(uc, monkeypatch)
+
+
+def test_update_case_table_has_one_entry_per_compiled_kernel():
+    """tests/update_cases.py: its keys are exactly the kernels of the code object, and the dims of every entry make
+    ts_describe_step_update name the entry's key - with the float32 and with the uint8 output set."""
+    from tiler_slider_amd import _cabi, _update_cabi as uc
+    assert sorted(cases.CASES) == _kernel_names(uc.LIB_PATH) and len(cases.CASES) == uc.MIN_KERNELS
+    for name, (S, T, Tt, K) in cases.CASES.items():
+        assert 1 <= T <= S * S and K >= 0, name
+        for outputs, u8 in ((_cabi.OUT_OBS, False), (_cabi.OUT_OBS | _cabi.OUT_REWARD, False), (_cabi.OUT_OBS_U8, True),
+                            (_cabi.OUT_OBS_U8 | _cabi.OUT_REWARD | _cabi.OUT_FLAGS, True)):
+            for mc in (0, 1):
+                d = uc.describe_step_update(_dims(S, T, mc, 331, Tt=Tt), outputs)
+                assert (d["name"] == name) == (u8 == cases.is_u8(name)), (name, outputs, d["name"])
+    # the two observation types of a shape share their levels
+    assert len({cases.shape_key(n) for n in cases.CASES}) == 16
+    assert all(cases.shape_key(n) == cases.shape_key(n.replace("false", "true")) for n in cases.CASES)
+
+
+@pytest.mark.parametrize("name", sorted(n for n in cases.CASES if not cases.is_u8(n)))
+def test_update_case_levels_are_honest(oracle, name):
+    """What the GPU tests of a case can see, from the oracle alone, in both colour modes: 331 boards of the case's levels, 24
+    steps of the unpatched action stream, max_steps 6, autoreset mode - tiles move, boards win where the counts allow it and
+    never elsewhere, episodes time out and are reset.  The levels are well formed: cells inside the board, tiles apart, no tile
+    and no target on an obstacle."""
+    import numpy as np
+    S, T, Tt, K = cases.CASES[name]
+    N = 331
+    for mc in (True, False):
+        blk, init, tgt = cases.levels(oracle, name, N, mc)
+        assert blk.shape == ((S * S + 31) // 32, N) and init.shape == (T, N) and tgt.shape == (Tt, N)
+        assert init.dtype == tgt.dtype == np.uint8 and blk.dtype == np.uint32
+        assert int(init.max()) < S * S and (Tt == 0 or int(tgt.max()) < S * S or Tt > S * S)
+        wall = np.zeros((S * S, N), bool)
+        for p in range(S * S):
+            wall[p] = (blk[p >> 5] >> np.uint32(p & 31)) & 1
+        assert (wall.sum(axis=0) == K).all()
+        cols = np.arange(N)
+        for t in range(T):
+            assert not wall[init[t], cols].any(), (name, "a tile on an obstacle")
+            for u in range(t):
+                assert (init[t] != init[u]).all(), (name, "two tiles on one cell")
+        for j in range(Tt):
+            assert not wall[np.minimum(tgt[j], S * S - 1), cols].any(), (name, "a target on an obstacle")
+        ref = oracle.OracleBatch(S, mc, 6, blk, init, tgt)
+        ref.reset()
+        flags = np.stack([ref.step(oracle.fill_actions(N, seed=cases.ACTION_SEED, step_index=k), mode=oracle.MODE_AUTORESET,
+                                   obs=False)["flags"] for k in range(24)])
+        moved, wins, resets, timeouts = cases.assert_floors(name, mc, flags)
+        print(f"{name} {'multi' if mc else 'single'} colour: {moved:.2f} moved, {wins} wins, {resets} autoresets, {timeouts} timeouts")
 
 
 def test_graft_entry_builds_and_loads_the_ninth_library():
