@@ -7,10 +7,12 @@ native; constructing an environment loads lib/libtiler_slider_hip.so and lib/lib
 lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_slider_table.so, the first rollout()
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
 trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
-trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, and each fails loudly if its library is missing (no CPU fallback).
+trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
+lib/libtiler_slider_loss.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
+from ._loss_cabi import build_library as build_loss_library
 from ._policy_cabi import build_library as build_policy_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
@@ -24,6 +26,7 @@ from .actor_critic import ActorCriticNet
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
 from .gym_wrapper import GymVecTilerSlider
+from .loss import LossInfo, actor_critic_loss, actor_critic_loss_grads
 from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
 from .pipelined import PipelinedTilerSliderEnv
@@ -41,4 +44,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "DistanceTable", "build_table_library", "TABLE_MAX_DEPTH", "TABLE_INVALID", "TABLE_DEEP", "TABLE_NONE",
            "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library",
            "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
-           "ActorCriticNet", "build_ac_library", "build_update_library"]
+           "ActorCriticNet", "build_ac_library", "build_update_library",
+           "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library"]

@@ -1089,6 +1089,21 @@ class VecTilerSliderEnv:
         from .targets import trajectory_labels
         return trajectory_labels(self, rollout, table, rows)
 
+    def trajectory_loss(self, logits, rollout, targets=None, values=None, labels=None, clip=0.0, value_coef=0.5, entropy_coef=0.0,
+                        normalize_adv=False):
+        """LossInfo of the fused actor-critic loss (include/tiler_slider_loss.h: ts_actor_critic_loss, four launches, no float
+        atomics) between trajectory_outputs()' or trajectory_logits()' `logits` [K, N, 4] - and `values` [K, N] - and the targets
+        of `rollout`; its `.loss` carries one grad_fn, so `.loss.backward()` goes on into the network's own backward launch.
+        The actions are `labels` where given (uint8 [K, N], trajectory_labels()' action: a cross-entropy, 255 is no sample),
+        otherwise rollout.act_log.  `targets`, a TrajectoryReturns, gives the mask, the advantages and, with `values`, the returns
+        of value_coef (values - ret)^2; without it every sample with a move counts with advantage 1.  clip > 0 is PPO's clipped
+        ratio against the policy that played: the rollout must have logged its logits.  entropy_coef weighs the entropy bonus,
+        normalize_adv standardises the advantages over the live samples.  The plain-torch loss remains what it was; this
+        call is tiler_slider_amd.actor_critic_loss() with the arguments looked up, and raises ValueError where one is missing
+        or of another shape, dtype or device."""
+        from .loss import trajectory_loss
+        return trajectory_loss(self, logits, rollout, targets, values, labels, clip, value_coef, entropy_coef, normalize_adv)
+
     def _check_table(self, table, rows):
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
         from . import _table_cabi as tc

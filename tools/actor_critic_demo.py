@@ -2,7 +2,7 @@
 """An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
 episodes won per iteration.
 
-    python tools/actor_critic_demo.py [--shared] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
 
 The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
 
@@ -22,6 +22,10 @@ value head of its own, and an iteration is
     both losses' backward                                                           one launch
 
 The losses are plain torch on [K, N] floats: -(adv * logp(a)) and (v - ret)^2, both over the steps that played a transition.
+With --fused-loss they are ONE trajectory_loss() instead (four launches for the loss and its gradient, no
+float atomics), with the same hyper-parameters.  The torch path subtracts the advantages' mean; the fused loss has
+normalize_adv, which also divides by their standard deviation - so the curve of --fused-loss is NOT comparable line for line
+with the one of the torch path.  The torch path stays the default.
 No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
 """
 import argparse
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.97)
     ap.add_argument("--lam", type=float, default=0.9)
     ap.add_argument("--shared", action="store_true", help="one ActorCriticNet with a shared trunk instead of two PolicyNets")
+    ap.add_argument("--fused-loss", action="store_true", help="trajectory_loss() instead of the plain-torch losses (normalize_adv for the mean subtraction)")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
     import torch
@@ -70,7 +75,7 @@ def main():
         opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
     weights = RewardWeights(step=-0.01, win=1.0)
     say(f"{'one ActorCriticNet (shared trunk)' if args.shared else 'two PolicyNets'}: 256 solvable 4x4 levels, {args.steps} steps per iteration, H = {args.hidden}, Adam {args.lr}, gamma {args.gamma}, lambda {args.lam}, "
-        f"reward {tuple(weights)}")
+        f"reward {tuple(weights)}{', fused loss (normalize_adv)' if args.fused_loss else ''}")
     for it in range(args.iterations):
         out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
         if args.shared:
@@ -82,15 +87,22 @@ def main():
             with torch.no_grad():
                 last = env.trajectory_logits(critic)[0, :, 0].contiguous()      # the boards as they stand after the rollout
         tr = env.trajectory_returns(out, args.gamma, args.lam, values=v, last_value=last, reward=weights)
-        live = tr.mask.float()
-        count = live.sum().clamp(min=1)
-        adv = (tr.adv - (tr.adv * live).sum() / count) * live
-        logp = torch.log_softmax(logits if args.shared else env.trajectory_logits(actor, out), dim=2)
-        played = logp.gather(2, out.act_log.clamp(max=3).long().unsqueeze(2)).squeeze(2)
-        actor_loss = -(adv * played).sum() / count
-        critic_loss = (((v - tr.ret) ** 2) * live).sum() / count
-        opt.zero_grad()
-        (actor_loss + 0.5 * critic_loss).backward()
+        if args.fused_loss:
+            info = env.trajectory_loss(logits if args.shared else env.trajectory_logits(actor, out), out, tr, values=v.contiguous(),
+                                       value_coef=0.5, normalize_adv=True)
+            actor_loss, critic_loss = info.policy, info.value
+            opt.zero_grad()
+            info.loss.backward()
+        else:
+            live = tr.mask.float()
+            count = live.sum().clamp(min=1)
+            adv = (tr.adv - (tr.adv * live).sum() / count) * live
+            logp = torch.log_softmax(logits if args.shared else env.trajectory_logits(actor, out), dim=2)
+            played = logp.gather(2, out.act_log.clamp(max=3).long().unsqueeze(2)).squeeze(2)
+            actor_loss = -(adv * played).sum() / count
+            critic_loss = (((v - tr.ret) ** 2) * live).sum() / count
+            opt.zero_grad()
+            (actor_loss + 0.5 * critic_loss).backward()
         opt.step()
         share = float(out.wins.sum()) / max(1.0, float(out.finished.sum()))
         say(f"iteration {it:3d}: episodes won {share:6.3f} ({int(out.wins.sum())} of {int(out.finished.sum())}), actor loss {float(actor_loss):8.4f}, "
