@@ -183,10 +183,22 @@ def loss64(logits, act, mask=None, adv=None, old_logits=None, values=None, ret=N
     return Loss(dlogits, dvalues, scalars, live, dlogits_bound, dvalues_bound, scalars_bound, ambiguous, terms)
 
 
+def worst(err, bound):
+    """The largest error / bound over the entries whose bound is positive (0.0 if there is none).  Where a bound is exactly 0 -
+    value_coef = 0, an advantage standardised to 0 without an entropy term - the error must be exactly 0: no 0 / 0 enters a
+    ratio, and an error there makes the result infinite."""
+    err, bound = np.asarray(err, np.float64), np.asarray(bound, np.float64)
+    exact = bound == 0
+    if (err[exact] != 0).any():
+        return float("inf")
+    return float((err[~exact] / bound[~exact]).max()) if (~exact).any() else 0.0
+
+
 def loss32(logits, act, mask=None, adv=None, old_logits=None, values=None, ret=None, clip=0.0, value_coef=0.5, entropy_coef=0.0,
            normalize_adv=False, order=0):
     """A float32 NumPy evaluation of the definition: (dlogits, dvalues, scalars).  order 0 follows the formula as written
-    (p = exp(lp), sums left to right); order 1 takes p = e / s, sums the other way round and factors the gradient differently."""
+    (p = exp(lp), sums left to right); order 1 takes p = e / s, sums the other way round - the samples from the last to the first, as a binary tree - and factors the
+    gradient differently."""
     f32 = np.float32
     z = np.asarray(logits, f32).reshape(-1, 4)
     M = z.shape[0]
@@ -250,9 +262,18 @@ def loss32(logits, act, mask=None, adv=None, old_logits=None, values=None, ret=N
         lv = dv * dv
         dvalues = np.where(live, (f32(2) * c * f32(value_coef)) * dv if order == 0 else f32(2) * (c * (f32(value_coef) * dv)), f32(0)).astype(f32)
 
+    def tree(t):
+        """From the last sample to the first, halved until one is left: ceil(log2 M) levels.  (A running sum has M - 1 levels: its
+        a-priori error, (M - 1) u sum |t|, is beyond the scalar bound's 64 u sum |t| - and its premise of 24 levels - from M = 66.)"""
+        t = t[::-1]
+        while t.size > 1:
+            t = np.append(t, f32(0)) if t.size % 2 else t
+            t = t[0::2] + t[1::2]
+        return t[0] if t.size else f32(0)
+
     def tot(t):
         t = np.where(live, t, f32(0)).astype(f32)
-        return c * (t.sum(dtype=f32) if order == 0 else t[::-1].cumsum(dtype=f32)[-1] if M else f32(0))
+        return c * (t.sum(dtype=f32) if order == 0 else tree(t))
 
     spi, sv, sh = tot(lpi), tot(lv), tot(H)
     scalars = np.array([spi + f32(value_coef) * sv - beta * sh, spi, sv, sh, tot(kl), tot(cut), f32(count), mu], f32)
@@ -313,6 +334,57 @@ def case(mode, M, seed, scale=3.0, spread=None, void=0.2):
     for name in ("logits", "old_logits", "adv", "values", "ret"):
         if name in kw:
             kw[name] = kw[name].copy()
+            kw[name][~live] = np.nan
+    return kw
+
+
+NAMES = ("old", "val", "adv", "mask")
+# the sixteen (old, val, adv, mask) settings: one compiled body of k_loss_main each; (adv, mask) names k_loss_stats' four
+BODIES = tuple((o, v, a, m) for o in (0, 1) for v in (0, 1) for a in (0, 1) for m in (0, 1))
+# ... and the 24 configurations the tests run: every body, and every body with adv once more with normalize_adv
+CONFIGS = tuple((b, nz) for b in BODIES for nz in ((False, True) if b[2] else (False,)))
+# (clip, value_coef, entropy_coef) off the defaults: a narrow clip under a heavy value and entropy term; 1 - clip < 0, no weight
+# on the value term and an entropy penalty; a clip that never cuts
+COEFFICIENTS = ((0.05, 2.0, 0.3), (1.5, 0.0, -0.05), (1e30, 0.5, 0.0))
+STALES = (0.5, 3.0)
+
+
+def body_id(old, val, adv, mask, normalize=False):
+    """"old+val+adv+mask", "adv+mask", "none"; "-norm" behind a body that standardises its advantages."""
+    return ("+".join(n for n, on in zip(NAMES, (old, val, adv, mask)) if on) or "none") + ("-norm" if normalize else "")
+
+
+def case_of(old, val, adv, mask, M, seed, *, normalize=False, clip=0.2, value_coef=0.5, entropy_coef=0.01, stale=0.5, scale=3.0):
+    """Inputs for any of the sixteen bodies, by case()'s recipe: Gaussian logits of `scale`, about a tenth of the samples dead by
+    an action byte in {4, 200, 255} (drawn per sample) and, where there is a mask, another tenth by the mask; NaN in every float
+    input of a sample that is not live.  old_logits - logits is Gaussian of `stale`.  Every array is drawn whether the body takes
+    it or not, so two bodies of one seed share their logits and actions; sample 0 is always live, so that M = 1 is a sample."""
+    assert adv or not normalize, "normalize_adv needs adv"
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    z = (rng.standard_normal((M, 4)) * scale).astype(f32)
+    drift = rng.standard_normal((M, 4)) * stale
+    act = rng.integers(0, 4, M).astype(np.uint8)
+    byte = rng.choice(np.array([4, 200, 255], np.uint8), M)
+    dead, off = rng.random(M) < 0.1, rng.random(M) < 0.1
+    a, v, rt = (rng.standard_normal(M) * 0.7 + 0.3).astype(f32), rng.standard_normal(M).astype(f32), rng.standard_normal(M).astype(f32)
+    dead[:1] = off[:1] = False
+    act[dead] = byte[dead]
+    kw = dict(logits=z, act=act, entropy_coef=entropy_coef)
+    live = ~dead
+    if mask:
+        kw.update(mask=(~off).astype(np.uint8))
+        live &= ~off
+    if adv:
+        kw.update(adv=a)
+        if normalize:
+            kw.update(normalize_adv=True)
+    if old:
+        kw.update(old_logits=(z + drift).astype(f32), clip=clip)
+    if val:
+        kw.update(values=v, ret=rt, value_coef=value_coef)
+    for name in ("logits", "old_logits", "adv", "values", "ret"):
+        if name in kw:
             kw[name][~live] = np.nan
     return kw
 

@@ -1,7 +1,8 @@
 """The fused actor-critic loss on the GPU (lib/libtiler_slider_loss.so) against the float64 yardstick of tests/loss_reference.py:
-the exact case bit for bit, the three modes inside the a-priori bound at every size at which the grid takes another shape, the
-edge cases, determinism, raw calls into guarded memory, the autograd wrapper, and the loss end to end behind an
-ActorCriticNet against the plain-torch loss."""
+the exact case bit for bit, the three modes inside the a-priori bound at every size at which the grid takes another shape, each
+of the sixteen compiled bodies of k_loss_main (and the four of k_loss_stats) inside it, coefficients off the defaults, the
+relations that tie one body to another bit for bit, the edge cases, determinism, raw calls into guarded memory, the autograd
+wrapper, the routes of trajectory_loss, and the loss end to end behind an ActorCriticNet against the plain-torch loss."""
 import ctypes as C
 import functools
 
@@ -31,6 +32,23 @@ def _case(mode, M, spread=None):
     return kw, lr.loss64(**kw)
 
 
+def _seed(body, M):
+    return 3000 + 31 * lr.BODIES.index(tuple(body)) + M % 997
+
+
+@functools.lru_cache(maxsize=None)
+def _case_of(body, normalize, M, coefficients=None, stale=0.5):
+    """The same for one of the sixteen bodies (M <= 1285: the yardstick is computed)."""
+    assert M <= 1285
+    co = {} if coefficients is None else dict(zip(("clip", "value_coef", "entropy_coef"), coefficients))
+    kw = lr.case_of(*body, M, _seed(body, M), normalize=normalize, stale=stale, **co)
+    return kw, lr.loss64(**kw)
+
+
+# four more bodies for determinism and guarded memory: with the three modes they repeat all four bodies of k_loss_stats
+MORE_BODIES = {lr.body_id(*b): b for b in ((1, 0, 1, 0), (0, 1, 0, 1), (1, 1, 0, 0), (0, 0, 1, 1))}
+
+
 def _to(torch, kw):
     dev = torch.device("cuda", 0)
     return {k: torch.from_numpy(v).to(dev) if isinstance(v, np.ndarray) else v for k, v in kw.items()}
@@ -50,17 +68,19 @@ def _bits(a):
 
 def _hold(mode, M, want, scalars, dz, dv):
     """Gradients inside the per-entry bound on every live sample that is not ambiguous (at most 1 % are), exact zeros elsewhere;
-    scalars inside theirs.  Prints each figure before it asserts."""
+    scalars inside theirs.  Where a bound is exactly 0 the error must be exactly 0 (lr.worst: infinite otherwise).  Prints each
+    figure before it asserts."""
     ok = want.live & ~want.ambiguous
     assert want.ambiguous.sum() <= 0.01 * max(1, want.live.sum()), (mode, M, "ambiguous samples")
     err = np.abs(dz.astype(np.float64) - want.dlogits)
-    ratio = float((err[ok] / want.dlogits_bound[ok]).max()) if ok.any() else 0.0
+    ratio = lr.worst(err[ok], want.dlogits_bound[ok])
     rv = 0.0
     if dv is not None:
-        rv = float((np.abs(dv.astype(np.float64) - want.dvalues)[want.live] / want.dvalues_bound[want.live]).max()) if want.live.any() else 0.0
+        rv = lr.worst(np.abs(dv.astype(np.float64) - want.dvalues)[want.live], want.dvalues_bound[want.live])
     serr = np.abs(scalars.astype(np.float64) - want.scalars)
     print(f"{mode} M={M}: worst dlogits error / bound {ratio:.3f}, dvalues {rv:.3f}; scalars error / bound "
-          f"{[round(float(e / b), 3) if b else float(e) for e, b in zip(serr, want.scalars_bound)]}; ambiguous {int(want.ambiguous.sum())}")
+          f"{[round(float(e / b), 3) if b else float(e) for e, b in zip(serr, want.scalars_bound)]}; ambiguous {int(want.ambiguous.sum())}; "
+          f"cut share {float(scalars[5]):.4f} (yardstick {want.scalars[5]:.4f})")
     assert np.isfinite(dz).all() and (dz[~want.live] == 0).all()
     assert ratio <= 1.0, (mode, M, ratio)
     if dv is not None:
@@ -115,6 +135,124 @@ def test_a_logit_spread_of_200_gives_finite_outputs_inside_the_bound(torch_cuda,
     _hold(mode, 1285, want, *_run(torch_cuda, kw))
 
 
+# ---------------------------------------------------------------------------------------------- 2b. every compiled body
+_CONFIG_IDS = [lr.body_id(*b, nz) for b, nz in lr.CONFIGS]
+
+
+@pytest.mark.parametrize("M", (1, BLOCK + 1, 1285))
+@pytest.mark.parametrize("body, normalize", lr.CONFIGS, ids=_CONFIG_IDS)
+def test_every_body_lies_inside_the_bound(torch_cuda, body, normalize, M):
+    """k_loss_main picks one of sixteen bodies by which of old_logits, values, adv and mask are given, k_loss_stats one of four by
+    adv and mask: each of them, and each body with adv once more with normalize_adv, at one sample, at two blocks and at 1285."""
+    old, val, adv, mask = body
+    kw, want = _case_of(body, normalize, M)
+    assert [k in kw for k in ("old_logits", "values", "adv", "mask")] == [bool(x) for x in body]
+    scalars, dz, dv = _run(torch_cuda, kw)
+    _hold(lr.body_id(*body, normalize), M, want, scalars, dz, dv)
+    assert scalars[6] == want.live.sum() >= 1
+    if not adv:
+        assert scalars[7] == 0.0
+    if not old:
+        assert scalars[4] == 0.0 and scalars[5] == 0.0
+    assert (dv is None) == (not val)
+
+
+@pytest.mark.parametrize("stale", lr.STALES)
+@pytest.mark.parametrize("coefficients", lr.COEFFICIENTS, ids=lambda c: "clip={:g},value={:g},entropy={:g}".format(*c))
+def test_coefficients_off_the_defaults(torch_cuda, coefficients, stale):
+    """The full body with normalize_adv at 1285 samples: a narrow clip under a heavy value and entropy term, 1 - clip < 0 with
+    no weight on the value term and an entropy penalty, and a clip that never cuts; the old policy close by and far off."""
+    clip, value_coef, entropy_coef = coefficients
+    kw, want = _case_of((1, 1, 1, 1), True, 1285, coefficients, stale)
+    scalars, dz, dv = _run(torch_cuda, kw)
+    _hold("clip={:g},value={:g},entropy={:g},stale={:g}".format(*coefficients, stale), 1285, want, scalars, dz, dv)
+    if value_coef == 0.0:
+        assert (dv == 0).all()
+    if clip == 1e30:
+        assert scalars[5] == 0.0
+    if clip == 1.5 and stale == 3.0:    # the lower edge is negative and r is not: only the upper edge can cut
+        assert 0.0 < scalars[5] < 1.0 and 0.0 < want.scalars[5] < 1.0
+        assert abs(float(scalars[5]) - want.scalars[5]) <= want.scalars_bound[5]
+
+
+# ---------------------------------------------------------------------------------------------- 2c. one body against another
+# No tolerance and no float64 pass: every block strides twice, with a ragged end.
+RELATION_M = 2 * GRID + 3
+_EIGHT = [(a, b, c) for a in (0, 1) for b in (0, 1) for c in (0, 1)]
+
+
+def _three_id(names):
+    return lambda t: "+".join(n for n, on in zip(names, t) if on) or "none"
+
+
+def _live(kw):
+    return (kw["act"] <= 3) & ((kw["mask"] != 0) if "mask" in kw else True)
+
+
+def _same(a, b, scalars, what):
+    """(scalars, dlogits, dvalues) of two calls: the gradients and the scalars named bit for bit, and neither is empty."""
+    assert a[0][6] > 0.7 * RELATION_M and np.abs(a[1]).max() > 0, what
+    assert np.array_equal(_bits(a[1]), _bits(b[1])), (what, "dlogits")
+    assert np.array_equal(_bits(a[0][list(scalars)]), _bits(b[0][list(scalars)])), (what, a[0], b[0])
+
+
+@pytest.mark.parametrize("setting", _EIGHT, ids=_three_id(("old", "val", "adv")))
+def test_a_mask_of_all_ones_is_no_mask_bit_for_bit(torch_cuda, setting):
+    """Each body and each first pass that reads a mask against its twin that does not: all outputs and all eight scalars.
+    An edit of ts_loss.hip that fails it, by the source: `m = 0u` as the default of a body without a mask, in either kernel -
+    that body then has no live sample (count 0 from k_loss_stats, all-zero gradients from k_loss_main)."""
+    old, val, adv = setting
+    kw = lr.case_of(old, val, adv, 0, RELATION_M, _seed((old, val, adv, 0), RELATION_M))
+    a, b = _run(torch_cuda, kw), _run(torch_cuda, dict(kw, mask=np.ones(RELATION_M, np.uint8)))
+    _same(a, b, range(8), setting)
+    assert (a[2] is None and b[2] is None) if not val else np.array_equal(_bits(a[2]), _bits(b[2]))
+
+
+@pytest.mark.parametrize("setting", _EIGHT, ids=_three_id(("old", "val", "mask")))
+def test_an_adv_of_all_ones_is_no_adv_bit_for_bit(torch_cuda, setting):
+    """Not normalised.  The gradients and scalars 0-6; mu is 1 where there is an adv (the float64 sum of count ones over count)
+    and 0 where there is none.  An edit that fails it: `adv = 0.0f` as k_loss_main's default without adv - A is then 0 on one
+    side and 1 on the other, and so is g."""
+    old, val, mask = setting
+    kw = lr.case_of(old, val, 0, mask, RELATION_M, _seed((old, val, 0, mask), RELATION_M))
+    ones = np.where(_live(kw), np.float32(1), np.float32(np.nan))
+    a, b = _run(torch_cuda, kw), _run(torch_cuda, dict(kw, adv=ones))
+    _same(a, b, range(7), setting)
+    assert (a[2] is None and b[2] is None) if not val else np.array_equal(_bits(a[2]), _bits(b[2]))
+    assert a[0][7] == 0.0 and b[0][7] == 1.0
+
+
+@pytest.mark.parametrize("setting", _EIGHT, ids=_three_id(("val", "adv", "mask")))
+def test_old_logits_of_the_same_bits_are_no_old_logits_bit_for_bit(torch_cuda, setting):
+    """log r is an exact 0 and r an exact 1: nothing is cut, the KL is 0 and the gradient is that of -A log p.  The policy scalar is
+    not compared (-A on one side, -A log p on the other), nor the loss that contains it.  An edit that fails it: the clamp's
+    edges swapped, fmaxf(fminf(r, lo), hi) - it returns hi for r = 1, u2 = 1.2 A, and every sample of negative A is cut (g = 0,
+    clip_frac > 0); or `kl = r - d`, which is 1 here."""
+    val, adv, mask = setting
+    kw = lr.case_of(0, val, adv, mask, RELATION_M, _seed((0, val, adv, mask), RELATION_M))
+    a, b = _run(torch_cuda, kw), _run(torch_cuda, dict(kw, old_logits=kw["logits"].copy(), clip=0.2))
+    _same(a, b, (2, 3, 6, 7), setting)
+    assert (a[2] is None and b[2] is None) if not val else np.array_equal(_bits(a[2]), _bits(b[2]))
+    assert b[0][4] == 0.0 and b[0][5] == 0.0
+
+
+@pytest.mark.parametrize("setting", _EIGHT, ids=_three_id(("old", "adv", "mask")))
+def test_a_value_coef_of_zero_is_no_value_term_bit_for_bit(torch_cuda, setting):
+    """dlogits and the loss, policy, entropy, KL, cut, count and mu scalars (the loss adds 0 * a finite sum); dvalues all zero; the
+    value scalar against the float64 mean of (v - ret)^2 over the live samples, inside 64 * 2**-24 of itself.  An edit that
+    fails it: `k2 = 2.0f * c` (the coefficient dropped from dvalues), or `dv` for `dv * dv` in the VAL-only sum."""
+    old, adv, mask = setting
+    kw = lr.case_of(old, 1, adv, mask, RELATION_M, _seed((old, 1, adv, mask), RELATION_M), value_coef=0.0)
+    bare = {k: v for k, v in kw.items() if k not in ("values", "ret", "value_coef")}
+    a, b = _run(torch_cuda, bare), _run(torch_cuda, kw)
+    _same(a, b, (0, 1, 3, 4, 5, 6, 7), setting)
+    assert a[2] is None and (b[2] == 0).all() and a[0][2] == 0.0
+    live = _live(kw)
+    want = float(((kw["values"][live].astype(np.float64) - kw["ret"][live].astype(np.float64)) ** 2).mean())
+    print(f"value scalar {float(b[0][2])!r}, float64 {want!r}, error / bound {abs(float(b[0][2]) - want) / (64 * lr.U * want):.3f}")
+    assert want > 0.5 and abs(float(b[0][2]) - want) <= 64 * lr.U * want
+
+
 # ---------------------------------------------------------------------------------------------- 3. the edges
 @pytest.mark.parametrize("mode", lr.MODES)
 def test_no_live_sample_gives_zeros_and_no_nan(torch_cuda, mode):
@@ -158,25 +296,28 @@ def test_no_sample_at_all(torch_cuda):
 
 
 # ---------------------------------------------------------------------------------------------- 4. determinism
-@pytest.mark.parametrize("mode", lr.MODES)
+@pytest.mark.parametrize("mode", lr.MODES + tuple(MORE_BODIES))
 def test_two_identical_calls_agree_bit_for_bit_at_the_largest_size(torch_cuda, mode):
-    kw, _ = _case(mode, SIZES[-1])
+    if mode in MORE_BODIES:
+        kw = lr.case_of(*MORE_BODIES[mode], SIZES[-1], _seed(MORE_BODIES[mode], SIZES[-1]), normalize=bool(MORE_BODIES[mode][2]))
+    else:
+        kw, _ = _case(mode, SIZES[-1])
     a, b = _run(torch_cuda, kw), _run(torch_cuda, kw)
     for x, y in zip(a, b):
         assert (x is None and y is None) or np.array_equal(_bits(x), _bits(y))
 
 
 # ---------------------------------------------------------------------------------------------- 5. the raw C-ABI into guarded memory
-@pytest.mark.parametrize("mode", lr.MODES)
-@pytest.mark.parametrize("M", (1, 321, GRID + 259))
+@pytest.mark.parametrize("M, mode", [(M, mode) for mode in lr.MODES for M in (1, 321, GRID + 259)] + [(321, body) for body in MORE_BODIES])
 def test_raw_calls_into_guarded_memory(torch_cuda, mode, M):
     """Every buffer of the call between 256 guard bytes, M no multiple of 4, the outputs prefilled with NaN: the guards and the
-    inputs are as they were, the outputs are the yardstick's."""
+    inputs are as they were, the outputs are the yardstick's.  An input the body does not take is NULL, and so is dvalues
+    where there is no value term."""
     torch = torch_cuda
     from tiler_slider_amd import _loss_cabi as lc
     dev = torch.device("cuda", 0)
     assert M % 4
-    kw, want = _case(mode, M)
+    kw, want = _case_of(MORE_BODIES[mode], False, M) if mode in MORE_BODIES else _case(mode, M)
     ins = {k: v for k, v in kw.items() if isinstance(v, np.ndarray)}
     g = {k: _guarded(torch, dev, v) for k, v in ins.items()}
     outs = {"dlogits": np.full((M, 4), np.nan, np.float32), "scalars": np.full(8, np.nan, np.float32),
@@ -187,6 +328,7 @@ def test_raw_calls_into_guarded_memory(torch_cuda, mode, M):
     at = lambda k: g[k].data_ptr() + GUARD if k in g else None
     lin = lc.LossIn(at("logits"), at("old_logits"), at("act"), at("mask"), at("adv"), at("values"), at("ret"), M, kw.get("clip", 0.0),
                     kw.get("value_coef", 0.5), kw.get("entropy_coef", 0.0), int(kw.get("normalize_adv", False)))
+    assert ("dvalues" in g) == ("values" in ins) == ("ret" in ins)
     lout = lc.LossOut(at("dlogits"), at("dvalues"), at("scalars"), at("workspace"))
     assert lc.lib().ts_actor_critic_loss(C.byref(lin), C.byref(lout), torch.cuda.current_stream(dev).cuda_stream) == 0
     dz, scalars = _payload(g["dlogits"], np.float32, (M, 4)), _payload(g["scalars"], np.float32, (8,))
@@ -305,6 +447,72 @@ def test_end_to_end_the_grads_of_an_actor_critic_net_are_the_plain_torch_losses(
     with pytest.raises(ValueError):
         env.trajectory_loss(z, bare, values=z[..., 0].contiguous())
     env.close()
+
+
+def test_every_route_of_trajectory_loss_is_the_raw_call_on_the_inputs_it_documents(torch_cuda, oracle):
+    """The end-to-end test's setting.  trajectory_loss looks its arguments up - the actions or the labels, the mask and the
+    advantages of the targets, the returns where there are values, the rollout's logits where clip > 0 - and each route returns
+    the bits of actor_critic_loss_grads called by hand on those: all seven fields, and both gradients after backward()."""
+    torch = torch_cuda
+    from tiler_slider_amd import ActorCriticNet, LossInfo, RewardWeights, actor_critic_loss_grads
+    env = _boards(torch, oracle)
+    dev = env.device
+    net = ActorCriticNet(env.onehot_channels * 16, 16, dev, generator=torch.Generator(device=dev).manual_seed(3))
+    out = env.rollout_policy(5, net.policy(), select="sample", seed=5, log=("start", "pos", "act", "flags", "logits"))
+    with torch.no_grad():
+        logits, v = env.trajectory_outputs(net, out)
+        last = env.trajectory_outputs(net)[1][0]
+    tr = env.trajectory_returns(out, 0.97, 0.9, values=v, last_value=last, reward=RewardWeights(step=-0.01, win=1.0))
+    labels = env.trajectory_labels(out, env.build_table())[2]
+    assert bool((labels != 255).any()) and bool(tr.mask.any())
+    targets = dict(mask=tr.mask, adv=tr.adv)
+    routes = (("targets", (tr,), {}, dict(targets)),
+              ("targets, clip", (tr,), dict(clip=0.2), dict(targets, old_logits=out.logits_log, clip=0.2)),
+              ("targets, values, normalised", (tr,), dict(values=v, normalize_adv=True), dict(targets, values=v, ret=tr.ret, normalize_adv=True)),
+              ("labels", (), dict(labels=labels), {}),
+              ("targets, labels", (tr,), dict(labels=labels), dict(targets)))
+    for name, args, kw, by_hand in routes:
+        z = logits.clone().requires_grad_(True)
+        if "values" in kw:
+            kw["values"] = v.clone().requires_grad_(True)
+        info = env.trajectory_loss(z, out, *args, **kw)
+        want, dz, dv = actor_critic_loss_grads(logits, labels if "labels" in kw else out.act_log, **by_hand)
+        assert isinstance(info, LossInfo) and float(want.count) > 0, name
+        for field in LossInfo._fields:
+            assert torch.equal(getattr(info, field).detach().view(torch.int32), getattr(want, field).view(torch.int32)), (name, field)
+        info.loss.backward()
+        assert torch.equal(z.grad.view(torch.int32), dz.view(torch.int32)) and bool(dz.any()), name
+        assert (dv is None) == ("values" not in kw), name
+        if dv is not None:
+            assert torch.equal(kw["values"].grad.view(torch.int32), dv.view(torch.int32)) and bool(dv.any()), name
+    env.close()
+
+
+def test_inputs_that_start_one_float_into_a_buffer_give_the_bits_of_aligned_ones(torch_cuda):
+    """logits and old_logits 4-byte but not 16-byte aligned: the call reads an aligned copy of them (loss._aligned); adv, values and
+    ret one float in are read where they lie.  The result is that of aligned clones, and no buffer changes, inside the view or
+    outside it."""
+    torch = torch_cuda
+    from tiler_slider_amd import actor_critic_loss_grads
+    kw, _ = _case_of((1, 1, 1, 1), True, 1285)
+    t = _to(torch, kw)
+    names = ("logits", "old_logits", "adv", "values", "ret")
+    big, views = {}, {}
+    for k in names:
+        big[k] = torch.full((t[k].numel() + 9,), -7.25, dtype=torch.float32, device=t[k].device)
+        views[k] = big[k][1:1 + t[k].numel()].view(t[k].shape)
+        views[k].copy_(t[k])
+        assert views[k].is_contiguous() and views[k].data_ptr() % 16 == 4
+    before = {k: b.clone() for k, b in big.items()}
+    rest = {k: x for k, x in t.items() if k not in names}
+    act = rest.pop("act")
+    call = lambda src: actor_critic_loss_grads(src["logits"], act, **{k: src[k] for k in names[1:]}, **rest)
+    got, want = call(views), call({k: t[k].clone() for k in names})
+    for a, b in zip(got[0] + got[1:], want[0] + want[1:]):
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert float(got[0].count) > 1000 and bool(got[1].any()) and bool(got[2].any())
+    for k in names:
+        assert torch.equal(big[k].view(torch.int32), before[k].view(torch.int32)), k
 
 
 def test_fifty_steps_on_the_experts_labels_lower_the_cross_entropy(torch_cuda):
