@@ -47,6 +47,13 @@ def update_supported(dims, outputs):
     return True
 
 
+def full_body(dims):
+    """True where k_step_update steps `dims` through its straight-line body (csrc/ts_update.hip): two tiles and two targets on a
+    board of at least two cells, which is when the two-tile kernels are full.  Everything else, the eight-tile kernels
+    included, takes the general body of the same kernel; results never differ."""
+    return dims.n_tiles == 2 and dims.n_targets == 2 and dims.size * dims.size >= 2
+
+
 def describe_step_update(dims, outputs=_cabi.OUT_OBS):
     """dict of ts_describe_step_update(dims, outputs): the launch ts_step_update would make, in the record of
     _cabi.describe_launch.  No GPU needed."""

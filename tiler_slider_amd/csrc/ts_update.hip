@@ -7,9 +7,11 @@
 // (obstacle bitboard, target cells, in auto-reset mode the initial cells), the dynamic state (tile cells, step counter, done
 // latch), the action byte and the cells the observation displays (`shown`) - with every load issued before the first is
 // consumed (rows past the tile / target count read the last row, results unused: a predicate per row costs a memory round
-// trip per row, ts_rollout.hip), plays one step with the arithmetic of ts_core.h in the order of k_small, and stores the state
+// trip per row, ts_rollout.hip; only the initial cells wait, for the done latches of the wave), plays one step with the arithmetic of ts_core.h in the order of k_small, and stores the state
 // as ts_step does.  Tiles live in a register array of TMAX (2 or 8) walked by fully unrolled loops predicated on t < T (T is
-// uniform, so the predicates are scalar branches).
+// uniform, so the predicates are scalar branches); a board with two tiles and two targets takes a second, straight-line body
+// of the two-tile kernels, where those predicates are constants.  Every row of the state is addressed from a base pointer in
+// scalar registers and the lane's 32-bit offset in its block (profiles/update_requests.md has what each of these is worth).
 //
 // The observation is never written as a whole: for every cell a tile leaves or enters, the channel-1 value under the old
 // cells (`shown`) and under the new ones is evaluated, and the new value is stored where they differ - one scattered 4-byte
@@ -39,61 +41,91 @@ struct UArgs {
 };
 
 // The scattered observation stores.  Plain stores leave the touched lines dirty in the XCD's L2 until the end of the kernel;
-// -DTS_UPDATE_STORE_SC1 builds the agent-scope flavour (written through the L2) for the A/B of profiles/update_timing.md.
-__device__ __forceinline__ void put(float *dst, uint32_t v) {
-#if defined(TS_UPDATE_STORE_SC1)
-  asm volatile("global_store_dword %0, %1, off sc1" ::"v"(dst), "v"((float)v) : "memory");
+// -DTS_UPDATE_STORE_SC1 builds the agent-scope flavour (written through the L2) for the A/B of profiles/update_timing.md, and
+// -DTS_UPDATE_NO_PUT compiles them out: the time of everything else (profiles/update_requests.md).
+template <class P>
+__device__ __forceinline__ void put(P *dst, uint32_t v) {
+#if defined(TS_UPDATE_NO_PUT)
+  (void)dst, (void)v;
+#elif defined(TS_UPDATE_STORE_SC1)
+  __hip_atomic_store(dst, (P)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store_* ... sc1
 #else
-  *dst = (float)v;
-#endif
-}
-__device__ __forceinline__ void put(uint8_t *dst, uint32_t v) {
-#if defined(TS_UPDATE_STORE_SC1)
-  asm volatile("global_store_byte %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-#else
-  *dst = (uint8_t)v;
+  *dst = (P)v;
 #endif
 }
 
-template <int S, int TMAX, bool U8>
-__global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
+// Row `row` of a row-major [rows][N] array from board b0 on.  Everything here is uniform: the sum is scalar arithmetic, and
+// an access at(row_from(...), lane) takes the pointer from scalar registers and a 32-bit offset from the lane.  The empty
+// asm pins the pointer to a scalar register pair where it is formed: without it the compiler adds the lane's offset to the
+// array first and the row's offset to that, in 64-bit vector arithmetic (v_mad_u64_u32, v_lshl_add_u64).
+template <class P>
+using global_ptr = __attribute__((address_space(1))) P *;  // the asm hides where the pointer came from: say it is global memory
+template <class P>
+__device__ __forceinline__ global_ptr<P> row_from(P *base, int row, int64_t N, int64_t b0) {
+  global_ptr<P> p = (global_ptr<P>)(base + ((int64_t)row * N + b0));
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// Element i (< 256) of such a row: the byte offset is formed in 32 bits, next to the access, so that the access takes the
+// `offset register, scalar base` form in whichever basic block it lands (the asm keeps the offset from being shared as a
+// 64-bit value across blocks, where the instruction selector no longer sees that it is a 32-bit one).
+template <class P>
+__device__ __forceinline__ __attribute__((address_space(1))) P &at(global_ptr<P> row, uint32_t i) {
+  uint32_t bytes = i * (uint32_t)sizeof(P);
+  asm volatile("" : "+v"(bytes));
+  return *(global_ptr<P>)((global_ptr<char>)row + bytes);
+}
+
+// One board of one lane.  FULL: the board has as many tiles and targets as the lane keeps (T == MT == Tt == TMAX), so every
+// `t < T` / `j < Tt` predicate, every min(t, T - 1) row select and the `Tt > 0` branch is a constant and the unrolled loops
+// are straight-line code.  The colour mode, auto-reset and the reward stay uniform run-time branches in both bodies: each
+// is a scalar compare in front of a few instructions, and each would double the code once more.
+template <int S, int TMAX, bool U8, bool FULL>
+__device__ __forceinline__ void step_update_body(const UArgs &a) {
   using BB = ts::Bitboard<S>;
   using M = typename BB::mask_t;
   constexpr int C = BB::C;
   constexpr int MT = C < TMAX ? C : TMAX;  // tiles a lane keeps (T <= C)
   constexpr M kFull = C == 64 ? ~M(0) : (M(1) << (C & 63)) - 1;
+  static_assert(!FULL || MT == TMAX, "the straight-line body is for boards that can hold TMAX tiles");
 
   const int64_t N = a.N;
-  const int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (n - (int64_t)(threadIdx.x & (kWave - 1)) >= N) return;  // wave-uniform
+  const int64_t b0 = (int64_t)blockIdx.x * kThreads;  // the block's first board (b0 < N: blocks == ceil(N / 256))
+  const uint32_t tid = threadIdx.x;
+  const uint32_t here = (uint32_t)min(N - b0, (int64_t)kThreads);  // boards of this block, 1 .. 256
+  if ((tid & ~(uint32_t)(kWave - 1)) >= here) return;              // wave-uniform
   // lanes past the batch play a copy of the LAST board and write nothing
-  const bool live = n < N;
-  const int64_t nl = live ? n : N - 1;
-  const int T = a.T, Tt = a.Tt;  // 1 <= T <= MT, Tt <= TMAX
+  const bool live = tid < here;
+  const uint32_t ll = live ? tid : here - 1;
+  const int T = FULL ? MT : a.T, Tt = FULL ? TMAX : a.Tt;  // 1 <= T <= MT, Tt <= TMAX
   const bool mc = a.mc != 0, autoreset = a.autoreset != 0;
 
-  // ---- loads: all unconditional, all issued before the first one is consumed ----
-  const M blk = ts::load_obstacles<S>(a.blk, N, nl) & kFull;
+  // ---- loads: all but the initial cells unconditional and issued before the first one is consumed ----
+  M blk = at(row_from(a.blk, 0, N, b0), ll);
+  if constexpr (BB::wide) blk |= (M)at(row_from(a.blk, 1, N, b0), ll) << 32;
+  blk &= kFull;
   uint32_t p[MT], sh[MT], in[MT], tg[TMAX];  // p: the cells as they lie in memory (an id >= C stays until the board moves)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    p[t] = a.pos[(int64_t)min(t, T - 1) * N + nl];
-    sh[t] = a.shown[(int64_t)min(t, T - 1) * N + nl];
+    p[t] = at(row_from(a.pos, min(t, T - 1), N, b0), ll);
+    sh[t] = at(row_from(a.shown, min(t, T - 1), N, b0), ll);
     in[t] = 0;
-  }
-  if (autoreset) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) in[t] = a.init[(int64_t)min(t, T - 1) * N + nl];
   }
 #pragma unroll
   for (int j = 0; j < TMAX; ++j) tg[j] = 0;
   if (Tt > 0) {
 #pragma unroll
-    for (int j = 0; j < TMAX; ++j) tg[j] = a.tgt[(int64_t)min(j, Tt - 1) * N + nl];
+    for (int j = 0; j < TMAX; ++j) tg[j] = at(row_from(a.tgt, min(j, Tt - 1), N, b0), ll);
   }
-  int32_t sc = a.step_count[nl];
-  uint32_t done = a.done[nl];
-  const uint32_t act = a.actions[nl];
+  int32_t sc = at(row_from(a.step_count, 0, N, b0), ll);
+  uint32_t done = at(row_from(a.done, 0, N, b0), ll);
+  const uint32_t act = at(row_from(a.actions, 0, N, b0), ll);
+  // The initial cells only in a wave where some board resets (0.2 % of the board-steps of a long-episode batch, one wave in
+  // eight): a second round trip there, two loads fewer everywhere else.
+  if (autoreset && __ballot(done != 0) != 0) {  // wave-uniform
+#pragma unroll
+    for (int t = 0; t < MT; ++t) in[t] = at(row_from(a.init, min(t, T - 1), N, b0), ll);
+  }
 
   // ---- the step (environment.py:100-143), the order of k_small: done on entry, bad action, slide ----
   M tgm = 0, occ = 0;
@@ -148,6 +180,22 @@ __global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
 #pragma unroll
     for (int t = 0; t < MT; ++t) r[t] = q[t];
   }
+#if defined(TS_UPDATE_ARITH_TWICE)
+  // Ablation (profiles/update_requests.md): the slides once more, on operands the compiler cannot tell from the first ones,
+  // and both results alive up to the flag store.  The bit is never set: the two results are equal.
+  {
+    M occ_b = occ, blk_b = blk;
+    asm volatile("" : "+v"(occ_b), "+v"(blk_b));
+#pragma unroll
+    for (int t = 0; t < MT; ++t) {
+      if (t < T) {
+        uint32_t pb = pc[t];
+        asm volatile("" : "+v"(pb));
+        if ((uint32_t)ts::slide_cell<S>((int)pb, occ_b, blk_b, dir) != q[t]) flags |= 0x80u;
+      }
+    }
+  }
+#endif
 
   // ---- the observation delta: old cells = shown, new cells = r, both clamped as the encoder clamps ----
   uint32_t o[MT], c[MT];
@@ -159,9 +207,10 @@ __global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
     if (t < T) occ_new |= M(1) << c[t];
   }
   using obs_t = typename std::conditional<U8, uint8_t, float>::type;
-  obs_t *mine;  // channel 1 of cell 0 of this board
-  if constexpr (U8) mine = a.obs_u8 + (n * C * 3 + 1);
-  else mine = a.obs + (n * C * 3 + 1);
+  obs_t *block_obs;  // the block's first board: a uniform pointer
+  if constexpr (U8) block_obs = a.obs_u8 + b0 * (C * 3);
+  else block_obs = a.obs + b0 * (C * 3);
+  const uint32_t mine = tid * (uint32_t)(C * 3) + 1u;  // channel 1 of cell 0 of this board, from block_obs
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     if (t < T) {
@@ -175,9 +224,9 @@ __global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
         }
       }
       if (!mc) nv = nv ? 1u : 0u, ov = ov ? 1u : 0u;
-      if (live && nv != ov) put(mine + 3 * c[t], nv);
+      if (live && nv != ov) put(block_obs + (mine + 3u * c[t]), nv);
       // the cell it was drawn on, where no tile stands any more (else the line above stores that cell's value)
-      if (live && !((occ_new >> o[t]) & M(1))) put(mine + 3 * o[t], 0u);
+      if (live && !((occ_new >> o[t]) & M(1))) put(block_obs + (mine + 3u * o[t]), 0u);
     }
   }
 
@@ -204,22 +253,34 @@ __global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
         }
       }
     }
-    if (live) a.reward[n] = -sum;
+    if (live) at(row_from(a.reward, 0, N, b0), tid) = -sum;
   }
 
   if (!live) return;
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     if (t < T) {
-      if (touched) a.pos[(int64_t)t * N + n] = (uint8_t)r[t];
-      if (r[t] != sh[t]) a.shown[(int64_t)t * N + n] = (uint8_t)r[t];
+      if (touched) at(row_from(a.pos, t, N, b0), tid) = (uint8_t)r[t];
+      if (r[t] != sh[t]) at(row_from(a.shown, t, N, b0), tid) = (uint8_t)r[t];
     }
   }
   if (touched) {
-    a.step_count[n] = sc;
-    a.done[n] = (uint8_t)done;
+    at(row_from(a.step_count, 0, N, b0), tid) = sc;
+    at(row_from(a.done, 0, N, b0), tid) = (uint8_t)done;
   }
-  a.flags[n] = (uint8_t)flags;
+  at(row_from(a.flags, 0, N, b0), tid) = (uint8_t)flags;
+}
+
+// The kernel chooses its body once, on a uniform condition (full_body of _update_cabi.py says the same).  Only the two-tile
+// kernels have the straight-line body: unrolled over eight tiles without a branch it takes 89 to 108 registers where the
+// general body takes 62 to 74, and the registers of a kernel are those of its larger body - three waves per SIMD fewer for
+// every board the eight-tile kernels step, full or not.
+template <int S, int TMAX, bool U8>
+__global__ __launch_bounds__(kThreads) void k_step_update(const UArgs a) {
+  if constexpr (TMAX == 2 && S * S >= TMAX) {
+    if (a.T == TMAX && a.Tt == TMAX) return step_update_body<S, TMAX, U8, true>(a);
+  }
+  step_update_body<S, TMAX, U8, false>(a);
 }
 
 using Kernel = void (*)(const UArgs);

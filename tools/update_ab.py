@@ -2,7 +2,8 @@
 """Times the in-place step (include/tiler_slider_update.h) against the full-write step on one GPU: where is
 VecTilerSliderEnv(obs_update="auto") allowed to step in place?
 
-    python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1] [--only cfg1_1m]
+    python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1] [--define NAME[=VALUE] ...] [--library FILE]
+                              [--max-steps M] [--only cfg1_1m]
 
 Per shape two environments on the same levels (bench.py's LEVEL_SEED, multi colour, auto-reset, max_steps 2**30) and the same
 sixteen action buffers (ACTION_SEED): obs_update="inplace" (ts_step_update whatever the size of the buffer) and obs_update="full"
@@ -13,6 +14,10 @@ something else.
 
 --store sc1 loads a build of the library whose scattered observation stores are agent-scope stores (-DTS_UPDATE_STORE_SC1, built
 into build/variants/ through the guarded build on first use) instead of the shipped plain stores.
+--define NAME[=VALUE] (repeatable) does the same for any other build-time knob of csrc/ts_update.hip - the ablations of
+profiles/update_requests.md are -DTS_UPDATE_NO_PUT (the observation stores compiled out) and -DTS_UPDATE_ARITH_TWICE (the slides
+computed twice) - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps with a build of the library made
+elsewhere (the parent commit's, say).  --max-steps 7 times episodes that end every seventh step, so that most waves reset.
 profiles/update_ab.log is where a run of this script belongs; run it under `timeout`.
 """
 import argparse
@@ -49,18 +54,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--store", choices=("plain", "sc1"), default="plain")
+    ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]", help="-D knob of csrc/ts_update.hip; repeatable")
+    ap.add_argument("--library", default=None, help="a build of libtiler_slider_update.so to step with instead of the shipped one")
+    ap.add_argument("--max-steps", type=int, default=2**30)
+    ap.add_argument("--check", choices=("all", "state"), default=None,
+                    help="what the two environments must agree on before a shape is timed; state: flags and cells only, the default "
+                         "with -DTS_UPDATE_NO_PUT, whose build leaves the observation alone")
     ap.add_argument("--only", default=None, help="comma-separated names of SHAPES")
     ap.add_argument("--clock-warmup-ms", type=float, default=300.0)
     args = ap.parse_args()
     import torch
     from tiler_slider_amd import VecTilerSliderEnv, _cabi, _update_cabi
 
-    if args.store == "sc1":
-        variant = os.path.join(ROOT, "build", "variants", "libtiler_slider_update_sc1.so")
-        if not os.path.exists(variant):
-            _cabi.compile_guarded(_update_cabi.SRC, variant, defines=("-DTS_UPDATE_STORE_SC1=1",), work=os.path.dirname(variant),
+    defines = (["TS_UPDATE_STORE_SC1=1"] if args.store == "sc1" else []) + args.define
+    if args.library and defines:
+        ap.error("--library takes a finished build: no --store sc1 or --define with it")
+    if args.library:
+        _update_cabi.LIB_PATH = os.path.abspath(args.library)
+    elif defines:
+        tag = "sc1" if defines == ["TS_UPDATE_STORE_SC1=1"] else "_".join(d.replace("TS_UPDATE_", "").replace("=", "").lower() for d in defines)
+        variant = os.path.join(ROOT, "build", "variants", f"libtiler_slider_update_{tag}.so")
+        if not os.path.exists(variant) or os.path.getmtime(variant) < os.path.getmtime(_update_cabi.SRC):
+            _cabi.compile_guarded(_update_cabi.SRC, variant, defines=tuple("-D" + d for d in defines), work=os.path.dirname(variant),
                                   min_kernels=_update_cabi.MIN_KERNELS)
         _update_cabi.LIB_PATH = variant  # before the first lib(): this process steps with the variant
+
+    check = args.check or ("state" if any("NO_PUT" in d for d in defines) else "all")
 
     lines = []
 
@@ -76,7 +95,8 @@ def main():
     L = _cabi.lib()
     stream = torch.cuda.current_stream(dev).cuda_stream
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    say(f"# tools/update_ab.py --store {args.store}: {args.steps} timed steps after {args.warmup} warm-up steps, HIP events, us per step; "
+    say(f"# tools/update_ab.py --store {args.store}{''.join(' --define ' + d for d in args.define)}"
+        f"{' --max-steps %d' % args.max_steps if args.max_steps != 2**30 else ''}: {args.steps} timed steps after {args.warmup} warm-up steps, HIP events, us per step; "
         f"{torch.cuda.get_device_name(dev)}")
     say(f"# library: {os.path.relpath(_update_cabi.LIB_PATH, ROOT)}")
     say("# shape            boards  obs MiB  kernel (in place)              in place, rounds        full, rounds            in place  full    full / in place  auto")
@@ -94,7 +114,7 @@ def main():
     names = args.only.split(",") if args.only else list(SHAPES)
     for name in names:
         S, T, K, n = SHAPES[name]
-        kw = dict(size=S, num_tiles=T, num_obstacles=K, seed=LEVEL_SEED, multi_color=True, max_steps=2**30, device=dev, auto_reset=True)
+        kw = dict(size=S, num_tiles=T, num_obstacles=K, seed=LEVEL_SEED, multi_color=True, max_steps=args.max_steps, device=dev, auto_reset=True)
         inplace = VecTilerSliderEnv.random(n, obs_update="inplace", **kw)
         full = VecTilerSliderEnv.random(n, obs_update="full", **kw)
         auto_says = "in place" if VecTilerSliderEnv.in_place_pays(inplace._obs.numel() * 4, n, T) else "full"
@@ -106,7 +126,8 @@ def main():
         inplace.reset(), full.reset()
         for i in range(20):
             inplace.step_async(ring[i & 15]), full.step_async(ring[i & 15])
-        same = torch.equal(inplace._obs, full._obs) and torch.equal(inplace._flags, full._flags) and torch.equal(inplace.positions, full.positions)
+        same = ((check == "state" or torch.equal(inplace._obs, full._obs)) and torch.equal(inplace._flags, full._flags)
+                and torch.equal(inplace.positions, full.positions))
         if not same:
             say(f"{name}: the two environments DIFFER after 20 steps - not timed")
             continue
