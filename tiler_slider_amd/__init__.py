@@ -8,11 +8,12 @@ lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
 trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
 trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
-lib/libtiler_slider_loss.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
 from ._loss_cabi import build_library as build_loss_library
+from ._optim_cabi import build_library as build_optim_library
 from ._policy_cabi import build_library as build_policy_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
@@ -29,6 +30,7 @@ from .gym_wrapper import GymVecTilerSlider
 from .loss import LossInfo, actor_critic_loss, actor_critic_loss_grads
 from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
+from .optim import FusedAdam
 from .pipelined import PipelinedTilerSliderEnv
 from .policy import MlpPolicy
 from .render import TextRender
@@ -45,4 +47,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "Rollout", "build_rollout_library", "MlpPolicy", "build_policy_library",
            "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
            "ActorCriticNet", "build_ac_library", "build_update_library",
-           "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library"]
+           "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library",
+           "FusedAdam", "build_optim_library"]

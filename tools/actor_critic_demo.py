@@ -2,7 +2,7 @@
 """An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
 episodes won per iteration.
 
-    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--fused-optim] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
 
 The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
 
@@ -26,6 +26,9 @@ With --fused-loss they are ONE trajectory_loss() instead (DESIGN.md section 20: 
 float atomics), with the same hyper-parameters.  The torch path subtracts the advantages' mean; the fused loss has
 normalize_adv, which also divides by their standard deviation - so the curve of --fused-loss is NOT comparable line for line
 with the one of the torch path.  The torch path stays the default.
+With --fused-optim the optimiser is FusedAdam instead of torch.optim.Adam (the update and the zeroing of
+the gradients in ONE launch, the step count on the device); it may be combined with --shared --fused-loss.  The last line then
+reports the steps it applied and skipped.
 No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
 """
 import argparse
@@ -46,10 +49,11 @@ def main():
     ap.add_argument("--lam", type=float, default=0.9)
     ap.add_argument("--shared", action="store_true", help="one ActorCriticNet with a shared trunk instead of two PolicyNets")
     ap.add_argument("--fused-loss", action="store_true", help="trajectory_loss() instead of the plain-torch losses (normalize_adv for the mean subtraction)")
+    ap.add_argument("--fused-optim", action="store_true", help="FusedAdam instead of torch.optim.Adam: update and zero_grad in one launch")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
     import torch
-    from tiler_slider_amd import ActorCriticNet, PolicyNet, RewardWeights, TilerSliderEnvFactory
+    from tiler_slider_amd import ActorCriticNet, FusedAdam, PolicyNet, RewardWeights, TilerSliderEnvFactory
 
     lines = []
 
@@ -67,15 +71,19 @@ def main():
     env.reset()
     D = env.onehot_channels * 16
     gen = torch.Generator(device=dev).manual_seed(0)
+    Adam = FusedAdam if args.fused_optim else torch.optim.Adam
     if args.shared:
         actor = critic = ActorCriticNet(D, args.hidden, dev, generator=gen)
-        opt = torch.optim.Adam(actor.parameters(), lr=args.lr)
+        opt = Adam(actor.parameters(), lr=args.lr)
     else:
         actor, critic = PolicyNet(D, args.hidden, dev, generator=gen), PolicyNet(D, args.hidden, dev, generator=gen)
-        opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
+        opt = Adam(list(actor.parameters()) + list(critic.parameters()), lr=args.lr)
     weights = RewardWeights(step=-0.01, win=1.0)
     say(f"{'one ActorCriticNet (shared trunk)' if args.shared else 'two PolicyNets'}: 256 solvable 4x4 levels, {args.steps} steps per iteration, H = {args.hidden}, Adam {args.lr}, gamma {args.gamma}, lambda {args.lam}, "
-        f"reward {tuple(weights)}{', fused loss (normalize_adv)' if args.fused_loss else ''}")
+        f"reward {tuple(weights)}{', fused loss (normalize_adv)' if args.fused_loss else ''}{', FusedAdam' if args.fused_optim else ''}")
+    # FusedAdam leaves the gradients at zero itself: the first backward creates them, every later one adds to zeros
+    zero_grad = (lambda: None) if args.fused_optim else opt.zero_grad
+    step = (lambda: opt.step(zero_grad=True)) if args.fused_optim else opt.step
     for it in range(args.iterations):
         out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
         if args.shared:
@@ -91,7 +99,7 @@ def main():
             info = env.trajectory_loss(logits if args.shared else env.trajectory_logits(actor, out), out, tr, values=v.contiguous(),
                                        value_coef=0.5, normalize_adv=True)
             actor_loss, critic_loss = info.policy, info.value
-            opt.zero_grad()
+            zero_grad()
             info.loss.backward()
         else:
             live = tr.mask.float()
@@ -101,12 +109,14 @@ def main():
             played = logp.gather(2, out.act_log.clamp(max=3).long().unsqueeze(2)).squeeze(2)
             actor_loss = -(adv * played).sum() / count
             critic_loss = (((v - tr.ret) ** 2) * live).sum() / count
-            opt.zero_grad()
+            zero_grad()
             (actor_loss + 0.5 * critic_loss).backward()
-        opt.step()
+        step()
         share = float(out.wins.sum()) / max(1.0, float(out.finished.sum()))
         say(f"iteration {it:3d}: episodes won {share:6.3f} ({int(out.wins.sum())} of {int(out.finished.sum())}), actor loss {float(actor_loss):8.4f}, "
             f"critic loss {float(critic_loss):8.4f}")
+    if args.fused_optim:
+        say(f"FusedAdam: {int(opt.steps_applied)} steps applied, {int(opt.steps_skipped)} skipped, last gradient norm {float(opt.grad_norm):.4f}")
 
 
 if __name__ == "__main__":
