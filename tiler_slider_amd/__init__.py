@@ -8,7 +8,8 @@ lib/libtiler_slider_search.so, the first build_table() or lookup() lib/libtiler_
 lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() lib/libtiler_slider_policy.so, the first
 trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
 trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
-lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so,
+the first place_at_distance() lib/libtiler_slider_starts.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -18,6 +19,7 @@ from ._policy_cabi import build_library as build_policy_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
+from ._starts_cabi import build_library as build_starts_library
 from ._table_cabi import TABLE_DEEP, TABLE_INVALID, TABLE_MAX_DEPTH, TABLE_NONE
 from ._table_cabi import build_library as build_table_library
 from ._targets_cabi import build_library as build_targets_library
@@ -36,7 +38,7 @@ from .policy import MlpPolicy
 from .render import TextRender
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
-from .vec_env import DistanceTable, Rollout, StepInfo, VecTilerSliderEnv
+from .vec_env import DistanceTable, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
@@ -48,4 +50,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
            "ActorCriticNet", "build_ac_library", "build_update_library",
            "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library",
-           "FusedAdam", "build_optim_library"]
+           "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library"]

@@ -95,6 +95,29 @@ class DistanceTable:
         return self.dist.shape[0]
 
 
+class StartInfo:
+    """What VecTilerSliderEnv.place_at_distance() returns (include/tiler_slider_starts.h), device tensors of [N]: `count` int32, the
+    placements of the board's row whose distance lies in its band; `dist` uint8, the distance of the placement the board was put
+    on, 255 where it was not placed; `deepest` uint8, the largest distance of the row, 255 where it holds none; `placed` bool,
+    dist != 255, computed on first use."""
+    __slots__ = ("count", "dist", "deepest", "_placed")
+
+    def __init__(self, count, dist, deepest):
+        self.count, self.dist, self.deepest, self._placed = count, dist, deepest, None
+
+    @property
+    def placed(self):
+        if self._placed is None:
+            self._placed = self.dist != 255
+        return self._placed
+
+    def __iter__(self):
+        return iter((self.count, self.dist, self.deepest, self.placed))
+
+    def __repr__(self):
+        return f"StartInfo(count, dist, deepest, placed: [{self.count.shape[0]}])"
+
+
 class Rollout:
     """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
@@ -939,6 +962,43 @@ class VecTilerSliderEnv:
                    _ptr(action), binding=tc)
         self._sync_if_host()
         return moves, best, action
+
+    # ------------------------------------------------------------------ curriculum starts (lib/libtiler_slider_starts.so)
+    def place_at_distance(self, table, min_moves=1, max_moves=None, rows=None, band=None, seed=0, step_index=0, board_offset=0,
+                          only_done=False, set_initial=True):
+        """Put every board on a placement of its tiles, drawn uniformly among those whose distance to the win - read from `table`
+        (build_table) - lies in min_moves .. max_moves (max_moves=None: 252, the largest distance a table holds), in ONE launch
+        (include/tiler_slider_starts.h: ts_starts_place) and without a synchronisation: a StartInfo of count, dist, deepest and
+        placed.  A board whose row holds no such placement is not placed: it stands where it stood and reports dist 255.
+        `band` uint8 [2, N] on the device gives every board its own (min, max) and overrides the two numbers; `rows` int32 [N]
+        as lookup(); the draw is the action stream's at (seed, board_offset + n, step_index), so another step_index draws
+        again.  only_done=True places only the boards that are done - fresh starts between strict-mode rollouts.  A placed
+        board gets step_count 0 and done False, and with set_initial=True the placement becomes its level's initial cells:
+        reset() and the auto-reset return there.  The observation buffer shows the new cells afterwards (the full write of
+        reset()); the last step's `info` is left as it is."""
+        from . import _starts_cabi as sc
+        from ._table_cabi import TABLE_MAX_DEPTH
+        self._require_open()
+        dist_table, n_rows, rows = self._check_table(table, rows)
+        N = self.num_envs
+        lo, hi = int(min_moves), TABLE_MAX_DEPTH if max_moves is None else int(max_moves)
+        if not (0 <= lo <= TABLE_MAX_DEPTH and 0 <= hi <= TABLE_MAX_DEPTH):
+            raise ValueError(f"min_moves and max_moves must be 0..{TABLE_MAX_DEPTH}")
+        if band is not None:
+            if not (isinstance(band, torch.Tensor) and band.dtype == torch.uint8 and tuple(band.shape) == (2, N) and band.device == self.device):
+                raise ValueError(f"band must be a uint8 tensor of shape (2, {N}) on {self.device}")
+            band = band.contiguous()
+        count, dist, deepest = self._empty(N, torch.int32), self._empty(N, torch.uint8), self._empty(N, torch.uint8)
+        cfg = sc.StartsCfg(lo, hi, _ptr(band), sc.DONE if only_done else sc.ALL, 1, 1 if set_initial else 0, 0,
+                           int(seed) & (2 ** 64 - 1), int(step_index), int(board_offset))
+        out = sc.StartsOut(_ptr(count), _ptr(dist), _ptr(deepest))
+        self._call("ts_starts_place", C.byref(self._dims), C.byref(self._state), _ptr(dist_table), n_rows, _ptr(rows), C.byref(cfg),
+                   C.byref(out), binding=sc)
+        if self._obs is not None:
+            self.encode(out=self._obs)  # the full write reset() makes, and _sync_shown(): an environment that steps in place stays right
+        self._sync_if_host()
+        self._started = True
+        return StartInfo(count, dist, deepest)
 
     # ------------------------------------------------------------------ fused rollouts (lib/libtiler_slider_rollout.so)
     _ROLLOUT_STATS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags")

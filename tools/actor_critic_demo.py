@@ -2,7 +2,7 @@
 """An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
 episodes won per iteration.
 
-    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--fused-optim] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--fused-optim] [--curriculum] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
 
 The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
 
@@ -29,6 +29,12 @@ with the one of the torch path.  The torch path stays the default.
 With --fused-optim the optimiser is FusedAdam instead of torch.optim.Adam (the update and the zeroing of
 the gradients in ONE launch, the step count on the device); it may be combined with --shared --fused-loss.  The last line then
 reports the steps it applied and skipped.
+With --curriculum the episodes do not start where the levels say: the distance table of the 256 levels is
+built once, every board is put on a placement one move from the win (place_at_distance, band [1, 1], set_initial=True, so that
+the auto-reset inside a rollout returns there), and before every later iteration the boards that are done get a fresh placement
+(only_done=True).  The upper end of the band rises by one whenever the share of episodes won in the last rollout passes 0.8, up to
+the median over the levels of their deepest distance.  The share of episodes won is then a share at the CURRENT band: it is not
+comparable with the curves that start from the levels' own cells.
 No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
 """
 import argparse
@@ -50,6 +56,7 @@ def main():
     ap.add_argument("--shared", action="store_true", help="one ActorCriticNet with a shared trunk instead of two PolicyNets")
     ap.add_argument("--fused-loss", action="store_true", help="trajectory_loss() instead of the plain-torch losses (normalize_adv for the mean subtraction)")
     ap.add_argument("--fused-optim", action="store_true", help="FusedAdam instead of torch.optim.Adam: update and zero_grad in one launch")
+    ap.add_argument("--curriculum", action="store_true", help="start the episodes a band of moves from the win (place_at_distance); the band widens as the win rate passes 0.8")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
     import torch
@@ -84,7 +91,15 @@ def main():
     # FusedAdam leaves the gradients at zero itself: the first backward creates them, every later one adds to zeros
     zero_grad = (lambda: None) if args.fused_optim else opt.zero_grad
     step = (lambda: opt.step(zero_grad=True)) if args.fused_optim else opt.step
+    hi = hi_max = 1
+    if args.curriculum:
+        table = env.build_table()
+        start = env.place_at_distance(table, 1, hi, seed=0xC0DE, step_index=0)
+        hi_max = max(1, int(start.deepest[start.deepest != 255].float().median()))
+        say(f"curriculum: band [1, 1] to start with, {int(start.placed.sum())} of 256 boards placed, its upper end rises up to {hi_max} (the median deepest distance)")
     for it in range(args.iterations):
+        if args.curriculum and it:
+            env.place_at_distance(table, 1, hi, seed=0xC0DE, step_index=it, only_done=True)     # fresh starts for the boards that finished
         out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
         if args.shared:
             logits, v = env.trajectory_outputs(actor, out)                      # [K, N, 4] and [K, N], one launch
@@ -114,7 +129,9 @@ def main():
         step()
         share = float(out.wins.sum()) / max(1.0, float(out.finished.sum()))
         say(f"iteration {it:3d}: episodes won {share:6.3f} ({int(out.wins.sum())} of {int(out.finished.sum())}), actor loss {float(actor_loss):8.4f}, "
-            f"critic loss {float(critic_loss):8.4f}")
+            f"critic loss {float(critic_loss):8.4f}" + (f", band [1, {hi}]" if args.curriculum else ""))
+        if args.curriculum and share > 0.8 and hi < hi_max:
+            hi += 1
     if args.fused_optim:
         say(f"FusedAdam: {int(opt.steps_applied)} steps applied, {int(opt.steps_skipped)} skipped, last gradient norm {float(opt.grad_norm):.4f}")
 
