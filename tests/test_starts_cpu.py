@@ -1,39 +1,23 @@
-"""The curriculum starts without a GPU: the twelfth library's C-ABI (include/tiler_slider_starts.h), its refusals in the header's
+"""The curriculum starts without a GPU: the starts library's C-ABI (include/tiler_slider_starts.h), its refusals in the header's
 order, its launch plan, its code object, and the CPU yardstick's own properties (tests/starts_reference.py) on real tables."""
 import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import starts_reference as sref
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
+from cabi_harness import _dims, _kernel_metadata, _kernel_names, _struct_fields
 from conftest import ROOT
 from tiler_slider_amd import _starts_cabi as sc
 
 
-def _others():
-    from tiler_slider_amd import (_ac_cabi, _cabi, _loss_cabi, _optim_cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi,
-                                  _targets_cabi, _train_cabi, _update_cabi)
-    return ((_cabi, "tiler_slider.h", "ts_abi_version", 6), (_search_cabi, "tiler_slider_search.h", "ts_search_abi_version", 1),
-            (_table_cabi, "tiler_slider_table.h", "ts_table_abi_version", 1), (_rollout_cabi, "tiler_slider_rollout.h", "ts_rollout_abi_version", 1),
-            (_policy_cabi, "tiler_slider_policy.h", "ts_policy_abi_version", 1), (_train_cabi, "tiler_slider_train.h", "ts_train_abi_version", 1),
-            (_targets_cabi, "tiler_slider_targets.h", "ts_targets_abi_version", 1), (_ac_cabi, "tiler_slider_ac.h", "ts_ac_abi_version", 1),
-            (_update_cabi, "tiler_slider_update.h", "ts_update_abi_version", 1), (_loss_cabi, "tiler_slider_loss.h", "ts_loss_abi_version", 1),
-            (_optim_cabi, "tiler_slider_optim.h", "ts_optim_abi_version", 1))
-
-
-def test_starts_library_exports_what_its_header_declares_and_the_other_eleven_are_unchanged():
-    L = sc.lib()
-    declared = _declared("tiler_slider_starts.h")
-    assert declared == sorted(sc.EXPORTS) == _exported(sc.LIB_PATH)
-    assert L.ts_starts_abi_version() == sc.ABI_VERSION == 1
+def test_starts_library_exports_what_its_header_declares():
     header = open(os.path.join(ROOT, "include", "tiler_slider_starts.h")).read()
     assert '#include "tiler_slider_table.h"' in header
-    for name, value in (("TS_STARTS_ABI_VERSION", sc.ABI_VERSION), ("TS_STARTS_ALL", sc.ALL), ("TS_STARTS_DONE", sc.DONE),
+    for name, value in (("TS_STARTS_ALL", sc.ALL), ("TS_STARTS_DONE", sc.DONE),
                         ("TS_STARTS_PIECE_BYTES", sc.PIECE_BYTES), ("TS_STARTS_FORM_NONE", sc.FORM_NONE), ("TS_STARTS_FORM_WAVE", sc.FORM_WAVE)):
         assert int(re.search(rf"#define {name} (\d+)", header).group(1)) == value, name
     # the definition is in the header in full
@@ -41,13 +25,7 @@ def test_starts_library_exports_what_its_header_declares_and_the_other_eleven_ar
                    "(idx / C^t) % C", "0xd1b54a32d192ed03", "0x9e3779b97f4a7c15", "REFUSALS, in this order and before any HIP call"):
         assert phrase in header, phrase
     for struct, cls in (("ts_starts_cfg", sc.StartsCfg), ("ts_starts_out", sc.StartsOut), ("ts_starts_desc", sc.StartsDesc)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = []
-        for decl in body.split(";"):
-            if decl.strip():
-                names = re.sub(r"\[\w+\]", "", decl).replace("*", " ").split(",")
-                fields += [names[0].split()[-1]] + [x.strip() for x in names[1:]]
+        fields = _struct_fields(header, struct)
         assert fields == [f for f, _ in cls._fields_], struct
     assert (C.sizeof(sc.StartsCfg), C.sizeof(sc.StartsOut), C.sizeof(sc.StartsDesc)) == (56, 24, 104)
     assert [(f, getattr(sc.StartsCfg, f).offset) for f, _ in sc.StartsCfg._fields_] == [
@@ -58,10 +36,6 @@ def test_starts_library_exports_what_its_header_declares_and_the_other_eleven_ar
         ("form", 0), ("lanes_per_board", 4), ("boards_per_block", 8), ("threads_per_block", 12), ("bytes_per_lane", 16), ("passes", 20),
         ("states", 24), ("blocks", 32), ("name", 40)]
     assert dict(sc.StartsCfg._fields_)["seed"] is C.c_uint64
-    for binding, hdr, version, abi in _others():
-        assert _exported(binding.LIB_PATH) == _declared(hdr) == sorted(binding.EXPORTS), hdr
-        assert not set(declared) & set(binding.EXPORTS)
-        assert getattr(binding.lib(), version)() == binding.ABI_VERSION == abi, hdr
     import tiler_slider_amd as pkg
     assert callable(pkg.build_starts_library) and {"StartInfo", "build_starts_library"} <= set(pkg.__all__)
     assert callable(pkg.VecTilerSliderEnv.place_at_distance)
@@ -200,29 +174,10 @@ def test_describe_plans_lanes_and_passes_and_names_exactly_the_compiled_kernels(
 
 
 def test_the_starts_kernels_use_no_scratch_no_lds_and_no_agprs():
-    import tempfile
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        co = guard.unbundle(sc.LIB_PATH, wd)
-        notes = subprocess.run([f"{guard.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"^\s*\.name:\s+(\S*k_starts_place\S*)\s*$", notes, flags=re.M)
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    scratch = [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    agprs = [int(v) for v in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    vgprs = [int(v) for v in re.findall(r"\.vgpr_count:\s+(\d+)", notes)]
-    assert len(names) == len(lds) == len(scratch) == len(agprs) == len(vgprs) == sc.MIN_KERNELS
-    assert not any(lds) and not any(scratch) and not any(agprs), (lds, scratch, agprs)
-    assert not re.search(r"\.uses_dynamic_stack:\s+true", notes)
-    assert max(vgprs) <= 64, vgprs      # eight waves per SIMD
-
-
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_starts_library(monkeypatch):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(sc.LIB_PATH)
-    assert n_kernels >= sc.MIN_KERNELS
-    assert class_a == [] and class_b == []
-    _assert_build_goes_through_the_guard(sc, monkeypatch)
+    kernels = _kernel_metadata(sc.LIB_PATH)
+    assert len(kernels) == len([k for k in kernels if "k_starts_place" in k["name"]]) == sc.MIN_KERNELS
+    assert not any(k["group_segment_fixed_size"] or k["private_segment_fixed_size"] or k["agpr_count"] or k["uses_dynamic_stack"] for k in kernels), kernels
+    assert max(k["vgpr_count"] for k in kernels) <= 64, kernels      # eight waves per SIMD
 
 
 def test_the_byte_arithmetic_of_the_kernel_on_the_host(tmp_path):

@@ -1,26 +1,20 @@
-"""The distance-to-win tables without a GPU: the third library's C-ABI (include/tiler_slider_table.h), its launch plan, its code
+"""The distance-to-win tables without a GPU: the table library's C-ABI (include/tiler_slider_table.h), its launch plan, its code
 object, and the CPU yardstick (tests/table_reference.py) against the optimal move counts already in git."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
+from cabi_harness import _dims, _instruction_counts, _kernel_names
 from conftest import GOLDEN_DIR, ROOT
 
 
-def test_table_library_exports_what_its_header_declares_and_the_other_two_are_unchanged():
-    from tiler_slider_amd import _cabi, _search_cabi, _table_cabi
-    LT = _table_cabi.lib()
-    declared = _declared("tiler_slider_table.h")
-    assert declared == sorted(_table_cabi.EXPORTS) == _exported(_table_cabi.LIB_PATH)
-    assert LT.ts_table_abi_version() == _table_cabi.ABI_VERSION == 1
+def test_table_library_exports_what_its_header_declares():
+    from tiler_slider_amd import _table_cabi
     header = open(os.path.join(ROOT, "include", "tiler_slider_table.h")).read()
-    for name, value in (("TS_TABLE_ABI_VERSION", _table_cabi.ABI_VERSION), ("TS_TABLE_MAX_DEPTH", _table_cabi.TABLE_MAX_DEPTH),
+    for name, value in (("TS_TABLE_MAX_DEPTH", _table_cabi.TABLE_MAX_DEPTH),
                         ("TS_TABLE_INVALID", _table_cabi.TABLE_INVALID), ("TS_TABLE_DEEP", _table_cabi.TABLE_DEEP),
                         ("TS_TABLE_NONE", _table_cabi.TABLE_NONE), ("TS_TABLE_FORM_NONE", _table_cabi.FORM_NONE),
                         ("TS_TABLE_FORM_WAVE", _table_cabi.FORM_WAVE), ("TS_TABLE_FORM_BLOCK", _table_cabi.FORM_BLOCK),
@@ -29,11 +23,6 @@ def test_table_library_exports_what_its_header_declares_and_the_other_two_are_un
                         ("TS_TABLE_TUNE_BLOCK_BELOW_BOARDS", _table_cabi.TUNE_BLOCK_BELOW_BOARDS)):
         assert int(re.search(rf"#define {name} \(?(-?\d+)\)?", header).group(1)) == value, name
     assert (_table_cabi.TABLE_MAX_DEPTH, _table_cabi.TABLE_INVALID, _table_cabi.TABLE_DEEP, _table_cabi.TABLE_NONE) == (252, 253, 254, 255)
-    # the other two libraries: the symbols of their own headers and nothing of the tables, ABI versions as before
-    assert _exported(_cabi.LIB_PATH) == _declared("tiler_slider.h") == sorted(_cabi.EXPORTS)
-    assert _exported(_search_cabi.LIB_PATH) == _declared("tiler_slider_search.h") == sorted(_search_cabi.EXPORTS)
-    assert not set(declared) & (set(_cabi.EXPORTS) | set(_search_cabi.EXPORTS))
-    assert _cabi.lib().ts_abi_version() == 6 and _search_cabi.lib().ts_search_abi_version() == 1
     import tiler_slider_amd
     assert (tiler_slider_amd.TABLE_MAX_DEPTH, tiler_slider_amd.TABLE_INVALID, tiler_slider_amd.TABLE_DEEP, tiler_slider_amd.TABLE_NONE) == (252, 253, 254, 255)
     assert tiler_slider_amd.DistanceTable is not None and callable(tiler_slider_amd.build_table_library)
@@ -180,36 +169,10 @@ def test_table_tuning_knobs_choose_between_forms_only_where_both_exist():
             L.ts_table_tuning(k, v)
 
 
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_table_library(monkeypatch):
-    """The gfx950 hazard the step library's build guards against (profiles/r03_wrong_slide_isa.md): the table library goes through
-    the same guarded build, and its shipped code object is re-checked instruction by instruction here."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    from tiler_slider_amd import _table_cabi as tc
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(tc.LIB_PATH)
-    assert n_kernels >= tc.MIN_KERNELS  # the metadata was found and parsed
-    assert class_a == [] and class_b == []
-    _assert_build_goes_through_the_guard(tc, monkeypatch)
-
-
 def test_wave_form_has_no_block_barrier_and_the_lookup_no_lds():
-    import tempfile
     from tiler_slider_amd import _table_cabi as tc
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        dis = subprocess.run([f"{guard.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", guard.unbundle(tc.LIB_PATH, wd)], check=True,
-                             capture_output=True, text=True).stdout
-    barriers, lds, kernel = {}, {}, None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            kernel = m.group(1)
-            barriers.setdefault(kernel, 0)
-            lds.setdefault(kernel, 0)
-        elif kernel and re.search(r"\bs_barrier\b", line):
-            barriers[kernel] += 1
-        elif kernel and re.search(r"\bds_", line):
-            lds[kernel] += 1
+    counts = _instruction_counts(tc.LIB_PATH, (r"\bs_barrier\b", r"\bds_"))
+    barriers, lds = {k: v[0] for k, v in counts.items()}, {k: v[1] for k, v in counts.items()}
     wave = {k: v for k, v in barriers.items() if "k_table_wave" in k}
     block = {k: v for k, v in barriers.items() if "k_table_block" in k}
     look = {k: v for k, v in lds.items() if "k_table_lookup" in k}

@@ -1,15 +1,12 @@
-"""The trainable policies without a GPU: the sixth library's C-ABI (include/tiler_slider_train.h), its launch plans, its code
+"""The trainable policies without a GPU: the train library's C-ABI (include/tiler_slider_train.h), its launch plans, its code
 object, and the CPU yardstick's gradient bound (tests/train_reference.py) against float32 evaluations in several orders."""
 import ctypes as C
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from cabi_harness import _assert_build_goes_through_the_guard, _declared, _dims, _exported, _kernel_names
+from cabi_harness import _dims, _instruction_counts, _kernel_metadata, _kernel_names, _struct_fields
 from conftest import ROOT
 from tiler_slider_amd import _train_cabi  # noqa: F401  every test here, the yardstick's self-checks included, belongs to the training library
 
@@ -17,30 +14,16 @@ LDS_LIMIT = 65536
 MAX_STEPS = 65535
 
 
-def test_train_library_exports_what_its_header_declares_and_the_other_five_are_unchanged():
-    from tiler_slider_amd import _cabi, _policy_cabi, _rollout_cabi, _search_cabi, _table_cabi, _train_cabi as tc
-    L = tc.lib()
-    declared = _declared("tiler_slider_train.h")
-    assert declared == sorted(tc.EXPORTS) == _exported(tc.LIB_PATH)
-    assert L.ts_train_abi_version() == tc.ABI_VERSION == 1
+def test_train_library_exports_what_its_header_declares():
+    from tiler_slider_amd import _policy_cabi, _train_cabi as tc
     header = open(os.path.join(ROOT, "include", "tiler_slider_train.h")).read()
     assert '#include "tiler_slider_policy.h"' in header
-    assert int(re.search(r"#define TS_TRAIN_ABI_VERSION (\d+)", header).group(1)) == tc.ABI_VERSION
     assert "ORDER OF THE SUMS IS NOT PART OF THE CONTRACT" in header and "NOT reproducible bit for bit" in header
     for struct, cls in (("ts_train_in", tc.TrainIn), ("ts_mlp_grad", tc.MlpGrad), ("ts_train_desc", tc.TrainDesc)):
-        body = re.search(rf"typedef struct {struct} \{{(.*?)\}} {struct};", header, flags=re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = [re.search(r"(\w+)(\[\d+\])?$", decl.strip()).group(1) for decl in body.split(";") if decl.strip()]
+        fields = _struct_fields(header, struct)
         assert fields == [f for f, _ in cls._fields_], struct
     assert C.sizeof(tc.TrainIn) == 24 and C.sizeof(tc.MlpGrad) == 32 and C.sizeof(tc.TrainDesc) == 112
     assert tc.Mlp is _policy_cabi.Mlp
-    # the other five libraries: the symbols of their own headers and nothing of this one's, ABI versions as before
-    for binding, hdr in ((_cabi, "tiler_slider.h"), (_search_cabi, "tiler_slider_search.h"), (_table_cabi, "tiler_slider_table.h"),
-                         (_rollout_cabi, "tiler_slider_rollout.h"), (_policy_cabi, "tiler_slider_policy.h")):
-        assert _exported(binding.LIB_PATH) == _declared(hdr) == sorted(binding.EXPORTS), hdr
-        assert not set(declared) & set(binding.EXPORTS)
-    assert (_cabi.lib().ts_abi_version(), _search_cabi.lib().ts_search_abi_version(), _table_cabi.lib().ts_table_abi_version(),
-            _rollout_cabi.lib().ts_rollout_abi_version(), _policy_cabi.lib().ts_policy_abi_version()) == (6, 1, 1, 1, 1)
     import tiler_slider_amd
     assert tiler_slider_amd.PolicyNet is not None and callable(tiler_slider_amd.build_train_library)
     assert callable(tiler_slider_amd.VecTilerSliderEnv.trajectory_logits) and callable(tiler_slider_amd.MlpPolicy.from_kernel_layout)
@@ -241,31 +224,12 @@ def test_every_train_kernel_keeps_its_board_in_registers_and_its_lds_dynamic():
     (every byte of LDS is the dynamic allocation ts_describe_train_* reports), no accumulation registers (the hazard scan skips
     kernels that use them), and the float adds are single instructions: ds_add_f32 and global_atomic_add_f32 in every backward
     kernel, no compare-and-swap loop anywhere."""
-    import tempfile
     from tiler_slider_amd import _train_cabi as tc
-    from tiler_slider_amd import _vgpr_guard as guard
-    with tempfile.TemporaryDirectory() as wd:
-        co = guard.unbundle(tc.LIB_PATH, wd)
-        notes = subprocess.run([f"{guard.LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        dis = subprocess.run([f"{guard.LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
-    names = re.findall(r"^\s*\.name:\s+(\S*k_train_\S*)\s*$", notes, flags=re.M)
-    lds = [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)]
-    scratch = [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)]
-    agprs = [int(v) for v in re.findall(r"\.agpr_count:\s+(\d+)", notes)]
-    assert len(names) == len(lds) == len(scratch) == tc.MIN_KERNELS
-    assert not any(lds) and not any(scratch) and not any(agprs), (lds, scratch, agprs)
-    assert not re.search(r"\.uses_dynamic_stack:\s+true", notes)
+    kernels = _kernel_metadata(tc.LIB_PATH)
+    assert len(kernels) == len([k for k in kernels if "k_train_" in k["name"]]) == tc.MIN_KERNELS
+    assert not any(k["group_segment_fixed_size"] or k["private_segment_fixed_size"] or k["agpr_count"] or k["uses_dynamic_stack"] for k in kernels), kernels
     pats = (r"\bscratch_\w+", r"\bs_barrier\b", r"\bds_(read|write|load|store)\w*", r"\bds_add_f32\b", r"\bglobal_atomic_add_f32\b", r"cmpswap")
-    counts, kernel = {}, None
-    for line in dis.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
-        if m:
-            kernel = m.group(1)
-            counts.setdefault(kernel, [0] * len(pats))
-        elif kernel:
-            for i, pat in enumerate(pats):
-                counts[kernel][i] += bool(re.search(pat, line))
-    mine = {k: v for k, v in counts.items() if "k_train_" in k}
+    mine = {k: v for k, v in _instruction_counts(tc.LIB_PATH, pats).items() if "k_train_" in k}
     assert len(mine) == tc.MIN_KERNELS
     for k, (n_scratch, n_barrier, n_ds, n_ds_add, n_atomic, n_cas) in mine.items():
         assert n_scratch == 0 and n_ds > 0 and n_cas == 0, (k, n_scratch, n_ds, n_cas)
@@ -273,21 +237,6 @@ def test_every_train_kernel_keeps_its_board_in_registers_and_its_lds_dynamic():
             assert n_ds_add > 0 and n_atomic > 0 and n_barrier == 0, (k, n_ds_add, n_atomic, n_barrier)
         else:
             assert n_ds_add == 0 and n_atomic == 0 and 1 <= n_barrier <= 2, (k, n_ds_add, n_atomic, n_barrier)
-
-
-def test_no_64bit_read_of_the_last_allocated_vgpr_in_the_train_library(monkeypatch):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import scan_last_vgpr
-    from tiler_slider_amd import _train_cabi as tc
-    class_a, class_b, n_kernels = scan_last_vgpr.scan(tc.LIB_PATH)
-    assert n_kernels >= tc.MIN_KERNELS  # the metadata was found and parsed
-    assert class_a == [] and class_b == []
-    _assert_build_goes_through_the_guard(tc, monkeypatch)
-
-
-def test_graft_entry_builds_and_loads_the_sixth_library():
-    src = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert "_train_cabi" in src and '"ts_train_abi_version"' in src and "_smoke_train(" in src
 
 
 # ---------------------------------------------------------------------------------------------- the yardstick itself

@@ -1,10 +1,10 @@
 """ctypes binding of lib/libtiler_slider_ac.so — the actor-critic network's C-ABI declared in include/tiler_slider_ac.h.
 
-An eighth library beside the step, search, table, rollout, policy, train and targets libraries (all seven are pinned symbol by
-symbol and kernel by kernel, so the actor-critic kernels live in their own; the network they share with the policy and train
-libraries, value head included, is csrc/ts_mlp.h, listed through _train_cabi.HEADERS).  Same rules as _cabi.py: built through
-_cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is
-missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
+The network it shares with the policy and train libraries, value head included, is csrc/ts_mlp.h, listed through
+_train_cabi.HEADERS.
 """
 import ctypes as C
 import os
@@ -16,6 +16,7 @@ from ._train_cabi import Mlp, MlpGrad, TrainDesc, TrainIn
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_ac.hip")
 HEADERS = _train_cabi.HEADERS + [os.path.join(_cabi.ROOT, "include", "tiler_slider_ac.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_ac.so")
+HEADER, PREFIX, LABEL = "tiler_slider_ac.h", "ts_ac_", "actor-critic "
 
 ABI_VERSION = 1
 MIN_KERNELS = 16  # k_ac_forward<1 .. 8> and k_ac_backward<1 .. 8>: what compile_guarded must find
@@ -50,7 +51,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "actor-critic ", "ts_ac_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def ac_supported(dims, hidden):

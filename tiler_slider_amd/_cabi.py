@@ -15,9 +15,10 @@ ROOT = os.path.dirname(_PKG)
 SRC = os.path.join(_PKG, "csrc", "ts_kernels.hip")
 HEADERS = [os.path.join(_PKG, "csrc", "ts_core.h"), os.path.join(ROOT, "include", "tiler_slider.h")]
 LIB_PATH = os.path.join(_PKG, "lib", "libtiler_slider_hip.so")
-# what ts_search.hip, ts_table.hip and ts_rollout.hip share beyond ts_core.h: the index space and the host side of a launch
+# what every other library's source shares beyond ts_core.h: the index space and the host side of a launch
 SHARED_HEADERS = [os.path.join(_PKG, "csrc", h) for h in ("ts_index.h", "ts_launch.h")]
 
+HEADER, PREFIX, LABEL = "tiler_slider.h", "ts_", ""  # the public header, the symbol prefix, the library's name in the ABI-mismatch message
 ABI_VERSION = 6
 MIN_KERNELS = None  # hundreds of kernels: compile_guarded recognises a parse failure by "no kernel fills its allocation"
 OK, ERR_NULL, ERR_DIMS, ERR_LIMIT, ERR_HIP, ERR_ARG = 0, -1, -2, -3, -4, -5
@@ -187,12 +188,13 @@ def compile_guarded(src, out_lib, defines=(), work=None, verbose=False, keep_asm
     return report
 
 
-def bind(module, label, prefix, declare):
-    """(build_library, lib, check) of a binding module - this one or _search_cabi, _table_cabi, _rollout_cabi.  The module
-    keeps SRC, HEADERS, LIB_PATH, EXPORTS, ABI_VERSION, MIN_KERNELS and _lib as its own attributes, read when a function is
-    called; `label`: the library's name in the ABI-mismatch message; `prefix`: its <prefix>abi_version and
-    <prefix>last_hip_error symbols; declare(L): the prototypes of its entry points."""
+def bind(module, declare):
+    """(build_library, lib, check) of a binding module - this one or any other of _libraries.LIBRARIES.  The module keeps SRC,
+    HEADERS, LIB_PATH, EXPORTS, ABI_VERSION, MIN_KERNELS and _lib as its own attributes, read when a function is called, and
+    beside them HEADER (its public header's file name), PREFIX (of its <prefix>abi_version and <prefix>last_hip_error symbols)
+    and LABEL (the library's name in the ABI-mismatch message); declare(L): the prototypes of its entry points."""
     m = sys.modules[module]
+    label, prefix = m.LABEL, m.PREFIX
 
     def build_library(force=False, verbose=False):
         """Compile the library for gfx950 in-tree (hipcc cross-compiles without a GPU), through compile_guarded, if it is older
@@ -273,11 +275,11 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = bind(__name__, "", "ts_", _declare)
+build_library, lib, check = bind(__name__, _declare)
 
 
 def _status_string(rc):
-    """The text of a status code: the codes of all four libraries are the step library's."""
+    """The text of a status code: the codes of every library are the step library's."""
     return lib().ts_status_string(rc).decode()
 
 

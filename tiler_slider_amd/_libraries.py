@@ -1,0 +1,23 @@
+"""The C-ABI libraries of the package, in the order they were added: the one place that lists them.
+
+Every feature is a shared library of its own - its own .hip source, public header, binding module and lib/libtiler_slider_*.so -
+and stays one: a code object that is never recompiled with new neighbours keeps every kernel of every earlier feature byte for
+byte what was tested and measured (section 23 says what a binding module defines and how one is added).
+An entry is the binding module itself, so nothing a binding knows is restated here; __graft_entry__.build() and the CPU tests
+iterate over this tuple.
+"""
+from . import (_ac_cabi, _cabi, _loss_cabi, _optim_cabi, _policy_cabi, _rollout_cabi, _search_cabi, _starts_cabi, _table_cabi,
+               _targets_cabi, _train_cabi, _update_cabi)
+
+LIBRARIES = (_cabi, _search_cabi, _table_cabi, _rollout_cabi, _policy_cabi, _train_cabi, _targets_cabi, _ac_cabi, _update_cabi,
+             _loss_cabi, _optim_cabi, _starts_cabi)
+
+
+def name(binding):
+    """step, search, table, ...: _cabi is the step library's binding, _<name>_cabi every other's."""
+    return binding.__name__.rsplit(".", 1)[-1][1:-len("_cabi")] or "step"
+
+
+def build_all(force=False, verbose=False):
+    """build_library() of every entry, in order: each compiles only if it is stale (or `force`)."""
+    return [binding.build_library(force=force, verbose=verbose) for binding in LIBRARIES]

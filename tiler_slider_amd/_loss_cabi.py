@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_loss.so — the fused actor-critic loss' C-ABI declared in include/tiler_slider_loss.h.
 
-A tenth library beside the step, search, table, rollout, policy, train, targets, actor-critic and in-place-step libraries (all
-nine are pinned symbol by symbol and kernel by kernel, so the loss kernels live in their own).  Same rules as _cabi.py: built
-through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the
-library is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Desc
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_loss.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_loss.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_loss.so")
+HEADER, PREFIX, LABEL = "tiler_slider_loss.h", "ts_loss_", "loss "
 
 ABI_VERSION = 1
 MIN_KERNELS = 3  # k_loss_stats, k_loss_main and k_loss_finish: what compile_guarded must find
@@ -59,7 +59,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "loss ", "ts_loss_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def workspace_bytes(n_samples):

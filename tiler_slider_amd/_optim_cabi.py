@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_optim.so — the fused optimiser's C-ABI declared in include/tiler_slider_optim.h.
 
-An eleventh library beside the step, search, table, rollout, policy, train, targets, actor-critic, in-place-step and loss
-libraries (all ten are pinned symbol by symbol and kernel by kernel, so the optimiser's kernels live in their own).  Same rules
-as _cabi.py: built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no
-CPU fallback: if the library is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Desc
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_optim.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_optim.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_optim.so")
+HEADER, PREFIX, LABEL = "tiler_slider_optim.h", "ts_optim_", "optim "
 
 ABI_VERSION = 1
 MIN_KERNELS = 4  # k_optim_one, k_optim_norm, k_optim_apply and k_optim_finish: what compile_guarded must find
@@ -71,7 +71,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "optim ", "ts_optim_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def workspace_bytes(total_numel):

@@ -1,11 +1,10 @@
 """ctypes binding of lib/libtiler_slider_policy.so — the neural-policy rollouts' C-ABI declared in include/tiler_slider_policy.h.
 
-A fifth library beside libtiler_slider_hip.so, libtiler_slider_search.so, libtiler_slider_table.so and
-libtiler_slider_rollout.so (all four are pinned symbol by symbol and kernel by kernel, so the policy kernels live in their own).
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 The network's device functions and block plans are csrc/ts_mlp.h's, shared with the train and actor-critic libraries: HEADERS
 lists it, so editing it marks all of them (and the targets library, which extends the same list) stale.
-Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there
-is no CPU fallback: if the library is missing or does not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -18,6 +17,7 @@ SRC = os.path.join(_cabi._PKG, "csrc", "ts_policy.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi._PKG, "csrc", "ts_mlp.h")] + [
     os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h", "tiler_slider_rollout.h", "tiler_slider_policy.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_policy.so")
+HEADER, PREFIX, LABEL = "tiler_slider_policy.h", "ts_policy_", "policy "
 
 ABI_VERSION = 1
 POLICY_MAX_HIDDEN = 64
@@ -70,7 +70,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "policy ", "ts_policy_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def policy_supported(dims, hidden):

@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_rollout.so — the fused rollouts' C-ABI declared in include/tiler_slider_rollout.h.
 
-A fourth library beside libtiler_slider_hip.so, libtiler_slider_search.so and libtiler_slider_table.so (all three are pinned
-symbol by symbol and kernel by kernel, so the rollout kernels live in their own).  Same rules as _cabi.py: built through
-_cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library
-is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Desc, Dims, State
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_rollout.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h", "tiler_slider_rollout.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_rollout.so")
+HEADER, PREFIX, LABEL = "tiler_slider_rollout.h", "ts_rollout_", "rollout "
 
 ABI_VERSION = 1
 ROLLOUT_MAX_STEPS, ROLLOUT_MAX_SIZE, ROLLOUT_MAX_TILES = 65535, 8, 8
@@ -58,7 +58,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "rollout ", "ts_rollout_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def rollout_supported(dims, policy):

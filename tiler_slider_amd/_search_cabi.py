@@ -1,8 +1,8 @@
 """ctypes binding of lib/libtiler_slider_search.so — the solver's C-ABI declared in include/tiler_slider_search.h.
 
-A second library beside libtiler_slider_hip.so (the step library's code object is pinned kernel by kernel, so the solver's
-kernels live in their own).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR
-hazard scan and padding), and there is no CPU fallback: if the library is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -13,6 +13,7 @@ from ._cabi import Desc, Dims, State
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_search.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h",)]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_search.so")
+HEADER, PREFIX, LABEL = "tiler_slider_search.h", "ts_search_", "solver "
 
 ABI_VERSION = 1
 SOLVE_NONE, SOLVE_DEPTH = -1, -2
@@ -45,7 +46,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "solver ", "ts_search_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def solve_states(dims):

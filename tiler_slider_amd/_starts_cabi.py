@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_starts.so — the curriculum starts' C-ABI declared in include/tiler_slider_starts.h.
 
-A twelfth library beside the step, search, table, rollout, policy, train, targets, actor-critic, in-place-step, loss and
-optimiser libraries (all eleven are pinned symbol by symbol and kernel by kernel, so the placement kernels live in their own).
-Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and
-there is no CPU fallback: if the library is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -15,6 +14,7 @@ SRC = os.path.join(_cabi._PKG, "csrc", "ts_starts.hip")
 HEADERS = (_cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi._PKG, "csrc", "ts_bytes.h")]
            + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h", "tiler_slider_starts.h")])
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_starts.so")
+HEADER, PREFIX, LABEL = "tiler_slider_starts.h", "ts_starts_", "starts "
 
 ABI_VERSION = 1
 MIN_KERNELS = 8  # k_starts_place<1 .. 8>: what compile_guarded must find in the device assembly
@@ -54,7 +54,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "starts ", "ts_starts_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def starts_supported(dims):

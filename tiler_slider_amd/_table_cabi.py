@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_table.so — the distance-to-win tables' C-ABI declared in include/tiler_slider_table.h.
 
-A third library beside libtiler_slider_hip.so and libtiler_slider_search.so (both are pinned symbol by symbol and kernel by
-kernel, so the tables' kernels live in their own).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc
---offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is missing or does not
-load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Desc, Dims, State
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_table.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_table.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_table.so")
+HEADER, PREFIX, LABEL = "tiler_slider_table.h", "ts_table_", "table "
 
 ABI_VERSION = 1
 TABLE_MAX_DEPTH, TABLE_INVALID, TABLE_DEEP, TABLE_NONE = 252, 253, 254, 255
@@ -47,7 +47,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "table ", "ts_table_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def table_states(dims):

@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_targets.so — the trajectory targets' C-ABI declared in include/tiler_slider_targets.h.
 
-A seventh library beside the step, search, table, rollout, policy and train libraries (all six are pinned symbol by symbol and
-kernel by kernel, so the target kernels live in their own).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc
---offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is missing or does not load,
-every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Desc, Dims, State
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_targets.hip")
 HEADERS = _train_cabi.HEADERS + [os.path.join(_cabi.ROOT, "include", "tiler_slider_targets.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_targets.so")
+HEADER, PREFIX, LABEL = "tiler_slider_targets.h", "ts_targets_", "targets "
 
 ABI_VERSION = 1
 MIN_KERNELS = 16  # k_traj_returns<1 .. 8> and k_traj_labels<1 .. 8>: what compile_guarded must find
@@ -74,7 +74,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "targets ", "ts_targets_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def targets_supported(dims, which):

@@ -1,10 +1,9 @@
 """ctypes binding of lib/libtiler_slider_train.so — the trainable policies' C-ABI declared in include/tiler_slider_train.h.
 
-A sixth library beside the step, search, table, rollout and policy libraries (all five are pinned symbol by symbol and kernel by
-kernel, so the training kernels live in their own; the network they share with the policy library is csrc/ts_mlp.h, which
-_policy_cabi.HEADERS lists).  Same rules as _cabi.py: built through _cabi.compile_guarded (hipcc
---offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library is missing or does not load,
-every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
+The network it shares with the policy library is csrc/ts_mlp.h, which _policy_cabi.HEADERS lists.
 """
 import ctypes as C
 import os
@@ -16,6 +15,7 @@ from ._policy_cabi import Mlp
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_train.hip")
 HEADERS = _policy_cabi.HEADERS + [os.path.join(_cabi.ROOT, "include", "tiler_slider_train.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_train.so")
+HEADER, PREFIX, LABEL = "tiler_slider_train.h", "ts_train_", "train "
 
 ABI_VERSION = 1
 MIN_KERNELS = 16  # k_train_forward<1 .. 8> and k_train_backward<1 .. 8>: what compile_guarded must find
@@ -56,7 +56,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "train ", "ts_train_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def train_supported(dims, hidden):

@@ -1,9 +1,8 @@
 """ctypes binding of lib/libtiler_slider_update.so — the in-place step's C-ABI declared in include/tiler_slider_update.h.
 
-A ninth library beside the step, search, table, rollout, policy, train, targets and actor-critic libraries (the step library is
-pinned symbol by symbol and kernel by kernel, so the in-place kernels live in their own).  Same rules as _cabi.py: built through
-_cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding), and there is no CPU fallback: if the library
-is missing or does not load, every entry point raises.
+Built through _cabi.compile_guarded (hipcc --offload-arch=gfx950, VGPR hazard scan and padding) like every entry of
+_libraries.LIBRARIES, which says why it is a library of its own.  There is no CPU fallback: if the library is missing or does
+not load, every entry point raises.
 """
 import ctypes as C
 import os
@@ -14,6 +13,7 @@ from ._cabi import Dims, LaunchDesc, State, StepOut
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_update.hip")
 HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_update.h")]
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_update.so")
+HEADER, PREFIX, LABEL = "tiler_slider_update.h", "ts_update_", "update "
 
 ABI_VERSION = 1
 UPDATE_MAX_SIZE, UPDATE_MAX_TILES = 8, 8
@@ -34,7 +34,7 @@ def _declare(L):
 
 
 _lib = None
-build_library, lib, check = _cabi.bind(__name__, "update ", "ts_update_", _declare)
+build_library, lib, check = _cabi.bind(__name__, _declare)
 
 
 def update_supported(dims, outputs):

@@ -1229,9 +1229,9 @@ class VecTilerSliderEnv:
         return self._stage_actions(torch.tensor(vals, dtype=torch.uint8))
 
     def _call(self, name, *args, binding=_cabi):
-        """One C-ABI call on the current stream of the environment's device; `binding`: the library's module (_cabi, _search_cabi,
-        _table_cabi, _rollout_cabi).  (The device context manager is entered only when another device is current: with it a small
-        launch - ts_valid_moves4 takes 5 us on the GPU - cost three times its kernel.)"""
+        """One C-ABI call on the current stream of the environment's device; `binding`: the library's binding module.
+        (The device context manager is entered only when another device is current: with it a small launch - ts_valid_moves4
+        takes 5 us on the GPU - cost three times its kernel.)"""
         fn = self._fns.get(name)
         if fn is None:
             fn = self._fns[name] = getattr(binding.lib(), name)

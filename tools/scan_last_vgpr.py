@@ -4,8 +4,8 @@ instruction with a 64-bit operand that reads the last register of its kernel's V
 
     python tools/scan_last_vgpr.py [path/to/lib.so]        # exit code 1 when class A occurs
 
-The build itself runs the same scan twice (before and after padding) and fails on a hit; tests/test_cabi_and_host_logic.py
-runs it on the shipped library.
+The build itself runs the same scan twice (before and after padding) and fails on a hit; tests/test_libraries_cpu.py
+runs it on every shipped library.
 """
 import importlib.util
 import os
