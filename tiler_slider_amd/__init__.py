@@ -9,13 +9,15 @@ lib/libtiler_slider_rollout.so, the first policy_logits() or rollout_policy() li
 trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs() lib/libtiler_slider_ac.so, the first
 trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
 lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so,
-the first place_at_distance() lib/libtiler_slider_starts.so, and each fails loudly if its library is missing (no CPU fallback).
+the first place_at_distance() lib/libtiler_slider_starts.so, the first build_policy_table(), walk_actions() or score_policy()
+lib/libtiler_slider_ptable.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
 from ._loss_cabi import build_library as build_loss_library
 from ._optim_cabi import build_library as build_optim_library
 from ._policy_cabi import build_library as build_policy_library
+from ._ptable_cabi import build_library as build_ptable_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
@@ -35,6 +37,7 @@ from .moves import Move
 from .optim import FusedAdam
 from .pipelined import PipelinedTilerSliderEnv
 from .policy import MlpPolicy
+from .ptable import PolicyScore, PolicyTable
 from .render import TextRender
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
@@ -50,4 +53,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "PolicyNet", "build_train_library", "RewardWeights", "TrajectoryReturns", "build_targets_library",
            "ActorCriticNet", "build_ac_library", "build_update_library",
            "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library",
-           "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library"]
+           "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library",
+           "PolicyTable", "PolicyScore", "build_ptable_library"]

@@ -1098,6 +1098,35 @@ class VecTilerSliderEnv:
         from .policy import rollout_policy
         return rollout_policy(self, steps, policy, select, epsilon, seed, step_index, board_offset, stats, log, advance)
 
+    # ------------------------------------------------------------------ policy tables (lib/libtiler_slider_ptable.so)
+    def build_policy_table(self, policy, max_depth=252, max_bytes=4 << 30, logits=False):
+        """A PolicyTable: the greedy play of `policy` (an MlpPolicy, or a PolicyNet / ActorCriticNet through its .policy()) from
+        EVERY placement of every board's level, exactly, in two launches (include/tiler_slider_ptable.h: ts_ptable_actions, the
+        network once per placement; ts_ptable_walk, the outcome of following its moves).  `.dist` uint8 [N, states] has
+        build_table()'s format and codes - the moves the policy needs to the win, TABLE_NONE where greedy play never wins
+        (deterministic play ends in a cycle or stands still), TABLE_DEEP where it has not won within `max_depth` moves - so
+        lookup(), place_at_distance() and every other call that takes a DistanceTable take it as it is.  `.act` uint8 [N, states]
+        is the move on each placement (255 on an invalid one) and, with logits=True, `.logits` float32 [N, states, 4] the values
+        it was chosen from, bit-equal to policy_logits() on a board standing there.  Reads no tile and writes no state; no
+        sampling, no horizon, no start distribution.  max_bytes as build_table() (2 bytes per placement, 18 with the logits)."""
+        from .ptable import build_policy_table
+        return build_policy_table(self, policy, max_depth, max_bytes, logits)
+
+    def walk_actions(self, act, max_depth=252):
+        """build_policy_table()'s second launch alone, over a given action table: `act` uint8 [N, states] on the device, any bytes -
+        a move 0 .. 3 is played, anything else stands still - gives the PolicyTable of that tabular policy.  Walking the
+        expert's moves reproduces build_table()."""
+        from .ptable import walk_actions
+        return walk_actions(self, act, max_depth)
+
+    def score_policy(self, ptable, table):
+        """PolicyScore of a PolicyTable against the optimal DistanceTable of the same levels (build_table()), one launch
+        (ts_ptable_score), integers only and the same bits on every run: per level the valid, solvable, solved and optimally
+        solved placements, those on which the policy's move is one of the expert's, the excess moves, and `solved_share`,
+        `optimal_share`, `agreement` over all levels as 0-dim device tensors."""
+        from .ptable import score_policy
+        return score_policy(self, ptable, table)
+
     # ------------------------------------------------------------------ trainable policies (lib/libtiler_slider_train.so)
     def trajectory_logits(self, net, rollout=None):
         """float32 [K, N, 4]: the logits of `net` (a tiler_slider_amd.PolicyNet or an MlpPolicy) on every board-step of `rollout`

@@ -2,7 +2,7 @@
 """An actor-critic loop built from the library's five launches per iteration, on 256 solvable 4x4 levels; prints the share of
 episodes won per iteration.
 
-    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--fused-optim] [--curriculum] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
+    python tools/actor_critic_demo.py [--shared] [--fused-loss] [--fused-optim] [--curriculum] [--score-every K] [--iterations 60] [--steps 32] [--hidden 32] [--lr 1e-2] [--log FILE]
 
 The critic is a second PolicyNet whose output column 0 is read as V(s) ("a critic without a new kernel"):
 
@@ -35,6 +35,11 @@ the auto-reset inside a rollout returns there), and before every later iteration
 (only_done=True).  The upper end of the band rises by one whenever the share of episodes won in the last rollout passes 0.8, up to
 the median over the levels of their deepest distance.  The share of episodes won is then a share at the CURRENT band: it is not
 comparable with the curves that start from the levels' own cells.
+With --score-every K the current network is scored every K iterations, before the iteration's rollout, and once after the last
+(DESIGN.md section 24): build_policy_table(actor) and score_policy() against the distance table of the 256 levels - the greedy
+play of the network from EVERY placement of every level, exactly.  solved, optimal and agreement are shares of the solvable
+placements; they depend on neither the start distribution nor the auto-reset nor the step limit of the line they stand on, so
+they are comparable between runs and flags.  They score GREEDY play; the rollouts of the loop sample.
 No number here is asserted by a test; with --log profiles/actor_critic_demo.log a run is kept.
 """
 import argparse
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--fused-loss", action="store_true", help="trajectory_loss() instead of the plain-torch losses (normalize_adv for the mean subtraction)")
     ap.add_argument("--fused-optim", action="store_true", help="FusedAdam instead of torch.optim.Adam: update and zero_grad in one launch")
     ap.add_argument("--curriculum", action="store_true", help="start the episodes a band of moves from the win (place_at_distance); the band widens as the win rate passes 0.8")
+    ap.add_argument("--score-every", type=int, default=0, metavar="K", help="every K iterations: solved, optimal and agreement shares of the network's greedy play over all placements")
     ap.add_argument("--log", default=None)
     args = ap.parse_args()
     import torch
@@ -92,12 +98,21 @@ def main():
     zero_grad = (lambda: None) if args.fused_optim else opt.zero_grad
     step = (lambda: opt.step(zero_grad=True)) if args.fused_optim else opt.step
     hi = hi_max = 1
+    table = env.build_table() if args.curriculum or args.score_every else None
+
+    def say_score(it):
+        score = env.score_policy(env.build_policy_table(actor), table)    # three launches; no state is touched
+        say(f"before iteration {it:3d}: over all {int(score.solvable.sum())} solvable placements of the 256 levels, greedy play solves "
+            f"{float(score.solved_share):6.3f}, in the least number of moves {float(score.optimal_share):6.3f}, and its move is one of the expert's on "
+            f"{float(score.agreement):6.3f}; {int(score.excess.sum())} moves too many in all")
+
     if args.curriculum:
-        table = env.build_table()
         start = env.place_at_distance(table, 1, hi, seed=0xC0DE, step_index=0)
         hi_max = max(1, int(start.deepest[start.deepest != 255].float().median()))
         say(f"curriculum: band [1, 1] to start with, {int(start.placed.sum())} of 256 boards placed, its upper end rises up to {hi_max} (the median deepest distance)")
     for it in range(args.iterations):
+        if args.score_every and it % args.score_every == 0:
+            say_score(it)
         if args.curriculum and it:
             env.place_at_distance(table, 1, hi, seed=0xC0DE, step_index=it, only_done=True)     # fresh starts for the boards that finished
         out = env.rollout_policy(args.steps, actor.policy(), select="sample", seed=it, log=("start", "pos", "act", "flags"))
@@ -132,6 +147,8 @@ def main():
             f"critic loss {float(critic_loss):8.4f}" + (f", band [1, {hi}]" if args.curriculum else ""))
         if args.curriculum and share > 0.8 and hi < hi_max:
             hi += 1
+    if args.score_every:
+        say_score(args.iterations)
     if args.fused_optim:
         say(f"FusedAdam: {int(opt.steps_applied)} steps applied, {int(opt.steps_skipped)} skipped, last gradient norm {float(opt.grad_norm):.4f}")
 
