@@ -11,7 +11,8 @@ from . import _cabi
 from ._cabi import Dims, LaunchDesc, State, StepOut
 
 SRC = os.path.join(_cabi._PKG, "csrc", "ts_update.hip")
-HEADERS = _cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_update.h")]
+HEADERS = (_cabi.HEADERS + _cabi.SHARED_HEADERS + [os.path.join(_cabi._PKG, "csrc", "ts_quad.h")]
+           + [os.path.join(_cabi.ROOT, "include", h) for h in ("tiler_slider_search.h", "tiler_slider_update.h")])
 LIB_PATH = os.path.join(_cabi._PKG, "lib", "libtiler_slider_update.so")
 HEADER, PREFIX, LABEL = "tiler_slider_update.h", "ts_update_", "update "
 

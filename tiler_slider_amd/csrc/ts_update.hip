@@ -16,8 +16,18 @@
 // The observation is never written as a whole: for every cell a tile leaves or enters, the channel-1 value under the old
 // cells (`shown`) and under the new ones is evaluated, and the new value is stored where they differ - one scattered 4-byte
 // (float32) or 1-byte (uint8) store per changed cell.  Most boards store nothing or two cells.
+//
+// Who stores them.  In the eight-tile kernels every lane stores the cells of its own board: the 64 active lanes of one store
+// instruction then address 64 different boards, no two of them inside one 64-byte piece, and every changed cell is a write
+// request of its own into the L2.  In the two-tile kernels (both bodies, both observation types) a lane packs what its board
+// has to store - at most four cells: per tile the cell it enters and the cell it leaves - into one descriptor word (ts_quad.h)
+// and stores nothing itself.  Where the wave has reconverged, four passes follow: in pass j the four lanes of every quad take
+// the descriptor of the quad's lane j by a quad-broadcast DPP move (v_mov_b32_dpp quad_perm:[j,j,j,j]: registers only, no LDS)
+// and lane k of the quad stores slot k of it, so that the up to four stores of one board leave in one instruction, inside that
+// board's 3 C elements.  Four store instructions per wave, as with per-lane stores; the same addresses and the same values.
 #include "../../include/tiler_slider_update.h"
 #include "ts_launch.h"
+#include "ts_quad.h"
 
 namespace {
 
@@ -43,6 +53,15 @@ struct UArgs {
 // The scattered observation stores.  Plain stores leave the touched lines dirty in the XCD's L2 until the end of the kernel;
 // -DTS_UPDATE_STORE_SC1 builds the agent-scope flavour (written through the L2) for the A/B of profiles/update_timing.md, and
 // -DTS_UPDATE_NO_PUT compiles them out: the time of everything else (profiles/update_requests.md).
+// Who issues them.  The two-tile kernels: the four lanes of a quad, one slot each of one board's descriptor, board after board
+// (the file comment).  -DTS_UPDATE_LANE_PUT builds them as the eight-tile kernels are built: every lane stores its own board's
+// cells (profiles/update_requests.md, section 5, has the two side by side).
+template <int TMAX>
+#if defined(TS_UPDATE_LANE_PUT)
+constexpr bool kQuadStore = false;
+#else
+constexpr bool kQuadStore = TMAX == 2;
+#endif
 template <class P>
 __device__ __forceinline__ void put(P *dst, uint32_t v) {
 #if defined(TS_UPDATE_NO_PUT)
@@ -211,6 +230,7 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   if constexpr (U8) block_obs = a.obs_u8 + b0 * (C * 3);
   else block_obs = a.obs + b0 * (C * 3);
   const uint32_t mine = tid * (uint32_t)(C * 3) + 1u;  // channel 1 of cell 0 of this board, from block_obs
+  uint32_t word = 0;                                   // kQuadStore: what this board has to store (ts_quad.h)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     if (t < T) {
@@ -224,10 +244,30 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
         }
       }
       if (!mc) nv = nv ? 1u : 0u, ov = ov ? 1u : 0u;
-      if (live && nv != ov) put(block_obs + (mine + 3u * c[t]), nv);
-      // the cell it was drawn on, where no tile stands any more (else the line above stores that cell's value)
-      if (live && !((occ_new >> o[t]) & M(1))) put(block_obs + (mine + 3u * o[t]), 0u);
+      const bool enters = live && nv != ov;
+      // the cell it was drawn on, where no tile stands any more (else `enters` stores that cell's value)
+      const bool leaves = live && !((occ_new >> o[t]) & M(1));
+      if constexpr (kQuadStore<TMAX>) {
+        word |= ts::quad_word(ts::quad_slot(enters, c[t], nv), 2 * t) | ts::quad_word(ts::quad_slot(leaves, o[t], 0u), 2 * t + 1);
+      } else {
+        if (enters) put(block_obs + (mine + 3u * c[t]), nv);
+        if (leaves) put(block_obs + (mine + 3u * o[t]), 0u);
+      }
     }
+  }
+  if constexpr (kQuadStore<TMAX>) {
+    // Every lane is active here (lanes past the batch carry a word of zero and store for the live boards of their quad).
+    // Pass j: the quad's four lanes take the word of its lane j (v_mov_b32_dpp quad_perm:[j,j,j,j]: no LDS) and one slot each.
+    const uint32_t quad = (tid & ~3u) * (uint32_t)(C * 3) + 1u;  // channel 1 of cell 0 of the quad's first board
+    const uint32_t my_slot = tid & 3u;
+    auto pass = [&](auto j) {  // j: a constant, the DPP control is an immediate
+      const uint32_t theirs = (uint32_t)__builtin_amdgcn_mov_dpp((int)word, j * 0x55, 0xf, 0xf, true);
+      const uint32_t slot = ts::quad_slot_of(theirs, my_slot);
+      if (ts::quad_present(slot)) put(block_obs + (quad + (uint32_t)(j * C * 3) + 3u * ts::quad_cell(slot)), ts::quad_value(slot));
+    };
+    static_assert(ts::kQuadSlots == 4, "one pass per lane of a quad");
+    pass(std::integral_constant<int, 0>{}), pass(std::integral_constant<int, 1>{});
+    pass(std::integral_constant<int, 2>{}), pass(std::integral_constant<int, 3>{});
   }
 
   // ---- build-defined Manhattan reward of the cells after the step (include/tiler_slider.h: ts_reward) ----

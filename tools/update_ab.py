@@ -2,7 +2,7 @@
 """Times the in-place step (include/tiler_slider_update.h) against the full-write step on one GPU: where is
 VecTilerSliderEnv(obs_update="auto") allowed to step in place?
 
-    python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1] [--define NAME[=VALUE] ...] [--library FILE]
+    python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1|lane] [--define NAME[=VALUE] ...] [--library FILE]
                               [--max-steps M] [--only cfg1_1m]
 
 Per shape two environments on the same levels (bench.py's LEVEL_SEED, multi colour, auto-reset, max_steps 2**30) and the same
@@ -13,7 +13,8 @@ shape is timed the two environments are compared after 20 steps (observation, fl
 something else.
 
 --store sc1 loads a build of the library whose scattered observation stores are agent-scope stores (-DTS_UPDATE_STORE_SC1, built
-into build/variants/ through the guarded build on first use) instead of the shipped plain stores.
+into build/variants/ through the guarded build on first use) instead of the shipped plain stores; --store lane one whose two-tile
+kernels store every board's cells from the board's own lane (-DTS_UPDATE_LANE_PUT) instead of from the four lanes of its quad.
 --define NAME[=VALUE] (repeatable) does the same for any other build-time knob of csrc/ts_update.hip - the ablations of
 profiles/update_requests.md are -DTS_UPDATE_NO_PUT (the observation stores compiled out) and -DTS_UPDATE_ARITH_TWICE (the slides
 computed twice) - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps with a build of the library made
@@ -53,7 +54,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--store", choices=("plain", "sc1"), default="plain")
+    ap.add_argument("--store", choices=("plain", "sc1", "lane"), default="plain")
     ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]", help="-D knob of csrc/ts_update.hip; repeatable")
     ap.add_argument("--library", default=None, help="a build of libtiler_slider_update.so to step with instead of the shipped one")
     ap.add_argument("--max-steps", type=int, default=2**30)
@@ -66,13 +67,14 @@ def main():
     import torch
     from tiler_slider_amd import VecTilerSliderEnv, _cabi, _update_cabi
 
-    defines = (["TS_UPDATE_STORE_SC1=1"] if args.store == "sc1" else []) + args.define
+    store_define = {"sc1": "TS_UPDATE_STORE_SC1=1", "lane": "TS_UPDATE_LANE_PUT=1"}
+    defines = ([store_define[args.store]] if args.store in store_define else []) + args.define
     if args.library and defines:
         ap.error("--library takes a finished build: no --store sc1 or --define with it")
     if args.library:
         _update_cabi.LIB_PATH = os.path.abspath(args.library)
     elif defines:
-        tag = "sc1" if defines == ["TS_UPDATE_STORE_SC1=1"] else "_".join(d.replace("TS_UPDATE_", "").replace("=", "").lower() for d in defines)
+        tag = args.store if defines == [store_define.get(args.store)] else "_".join(d.replace("TS_UPDATE_", "").replace("=", "").lower() for d in defines)
         variant = os.path.join(ROOT, "build", "variants", f"libtiler_slider_update_{tag}.so")
         if not os.path.exists(variant) or os.path.getmtime(variant) < os.path.getmtime(_update_cabi.SRC):
             _cabi.compile_guarded(_update_cabi.SRC, variant, defines=tuple("-D" + d for d in defines), work=os.path.dirname(variant),
