@@ -10,7 +10,8 @@ trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs()
 trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
 lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so,
 the first place_at_distance() lib/libtiler_slider_starts.so, the first build_policy_table(), walk_actions() or score_policy()
-lib/libtiler_slider_ptable.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, and each fails loudly if its library is
+missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -18,6 +19,8 @@ from ._loss_cabi import build_library as build_loss_library
 from ._optim_cabi import build_library as build_optim_library
 from ._policy_cabi import build_library as build_policy_library
 from ._ptable_cabi import build_library as build_ptable_library
+from ._reach_cabi import SOLVE_FULL
+from ._reach_cabi import build_library as build_reach_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
@@ -41,7 +44,7 @@ from .ptable import PolicyScore, PolicyTable
 from .render import TextRender
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
-from .vec_env import DistanceTable, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
+from .vec_env import DistanceTable, ReachResult, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
@@ -54,4 +57,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "ActorCriticNet", "build_ac_library", "build_update_library",
            "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library",
            "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library",
-           "PolicyTable", "PolicyScore", "build_ptable_library"]
+           "PolicyTable", "PolicyScore", "build_ptable_library",
+           "ReachResult", "SOLVE_FULL", "build_reach_library"]

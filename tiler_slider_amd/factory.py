@@ -54,14 +54,18 @@ class TilerSliderEnvFactory:
 
     @staticmethod
     def solvable_seeds(n, size=5, num_tiles=2, num_obstacles=3, multi_color=False, start_seed=0, min_moves=1, max_moves=None,
-                       device=None, batch_size=1 << 16):
+                       device=None, batch_size=1 << 16, capacity=4096):
         """The first `n` seeds >= start_seed, ascending (uint32 NumPy array), whose create_simple_env(size, num_tiles,
         num_obstacles, seed) level can be solved, in no fewer than `min_moves` and (if given) no more than `max_moves` moves.
         Most random levels cannot be solved at all (one in five at 4x4 with two tiles, one in ten at the reference's default
         shape: DESIGN.md section 11), and slides cannot be undone, so solvable levels have to be found: the seeds are turned into
         levels (ts_generate_mt19937) and solved (ts_solve) on the device, `batch_size` seeds at a time.  The result does not
         depend on batch_size.  Feed it to create_vec_env_from_seeds / VecTilerSliderEnv.from_seeds.  Raises ValueError when the
-        seeds run out at 2**32 first."""
+        seeds run out at 2**32 first.
+        Shapes ts_solve refuses - an index space above 65,536 placements - are solved by the hashed search instead
+        (ts_reach_solve, boards up to 8x8 with up to 8 tiles), each board within `capacity` reached states.  A board that reaches
+        more (SOLVE_FULL) is NOT a found seed, whether or not it can be solved: the result then depends on `capacity`, but never
+        on batch_size.  `capacity` plays no part for the shapes ts_solve takes."""
         import torch
         from . import _search_cabi as sc
         n, seed, batch_size = int(n), int(start_seed), max(1, int(batch_size))
@@ -75,7 +79,8 @@ class TilerSliderEnvFactory:
             seeds = np.arange(seed, min(seed + batch_size, 2**32), dtype=np.int64)
             env = VecTilerSliderEnv.from_seeds(seeds, size=size, num_tiles=num_tiles, num_obstacles=num_obstacles, multi_color=multi_color,
                                                device=device, obs_dtype=None)
-            moves, _ = env.solve_bits(depth, with_best=False)
+            hashed = sc.solve_states(env._dims) == 0
+            moves = env.solve_reachable(depth, capacity, with_best=False).moves if hashed else env.solve_bits(depth, with_best=False)[0]
             # (searched no deeper than max_moves: a longer optimum reads SOLVE_DEPTH, which is negative like SOLVE_NONE)
             hit = seeds[torch.nonzero(moves >= int(min_moves)).flatten().cpu().numpy()]
             found.append(hit)

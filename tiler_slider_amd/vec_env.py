@@ -118,6 +118,35 @@ class StartInfo:
         return f"StartInfo(count, dist, deepest, placed: [{self.count.shape[0]}])"
 
 
+class ReachResult:
+    """What VecTilerSliderEnv.solve_reachable() returns (include/tiler_slider_reach.h), tensors of [N]: `moves` int16 - 0 for a won
+    board, the least number of moves, SOLVE_NONE, SOLVE_DEPTH or SOLVE_FULL; `bits` uint8, bit a set where Move a starts a
+    shortest solution, and `best` bool [N, 4], its columns (both None when not asked for); `states` int32, the number of states
+    expanded; `expert` uint8, the lowest best move, 255 where there is none - step() takes it as it is."""
+    __slots__ = ("moves", "bits", "states", "_best", "_expert")
+
+    def __init__(self, moves, bits, states):
+        self.moves, self.bits, self.states, self._best, self._expert = moves, bits, states, None, None
+
+    @property
+    def best(self):
+        if self._best is None and self.bits is not None:
+            self._best = _bit_columns(self.bits)
+        return self._best
+
+    @property
+    def expert(self):
+        if self.bits is None:
+            raise ValueError("expert needs the best-move bits: solve_reachable(with_best=True)")
+        if self._expert is None:
+            lut = torch.tensor(VecTilerSliderEnv._LOWEST_MOVE, dtype=torch.uint8, device=self.bits.device)
+            self._expert = lut[self.bits.to(torch.int64)]
+        return self._expert
+
+    def __repr__(self):
+        return f"ReachResult(moves, best, bits, states: [{self.moves.shape[0]}])"
+
+
 class Rollout:
     """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
@@ -883,8 +912,8 @@ class VecTilerSliderEnv:
         self._require_open()
         if sc.solve_states(self._dims) == 0:
             raise ValueError(f"solve() searches boards up to {sc.SOLVE_MAX_SIZE}x{sc.SOLVE_MAX_SIZE} whose index space (size * size) ** n_tiles is at "
-                             f"most {sc.SOLVE_MAX_STATES}; {self.size}x{self.size} with {self.n_tiles} tiles is beyond that (a hash set in "
-                             "global memory would be a different kernel)")
+                             f"most {sc.SOLVE_MAX_STATES}; {self.size}x{self.size} with {self.n_tiles} tiles is beyond that (the hash set in "
+                             "global memory is a different kernel: solve_reachable())")
         if not 0 <= int(max_depth) <= sc.SOLVE_MAX_DEPTH:
             raise ValueError(f"max_depth must be 0..{sc.SOLVE_MAX_DEPTH}")
         moves = self._empty(self.num_envs, torch.int16)
@@ -902,6 +931,42 @@ class VecTilerSliderEnv:
         _, bits = self.solve_bits(max_depth)
         lut = torch.tensor(self._LOWEST_MOVE, dtype=torch.uint8, device=bits.device)
         return lut[bits.to(torch.int64)]
+
+    # ------------------------------------------------------------------ hashed solver (lib/libtiler_slider_reach.so)
+    def solve_reachable(self, max_depth=64, capacity=4096, with_best=True, workspace_bytes=1 << 30):
+        """solve() for boards whose index space is beyond it: breadth-first search of every board from its CURRENT cells with a
+        hash set in device memory (include/tiler_slider_reach.h: ts_reach_solve, one launch), which costs memory by what a board
+        reaches.  Returns a ReachResult: moves int16 [N] as solve()'s, or SOLVE_FULL where a board reached more than `capacity`
+        states before the search ended; best bool [N, 4] and bits uint8 [N] as solve() and solve_bits() (None with
+        with_best=False); states int32 [N], the number of states expanded; `.expert`, ready for step().  Single-colour boards are
+        not canonicalised: two orders of the same cells are two states.
+        The workspace is allocated here - one slice per board in flight, at most 1,024 boards and at most `workspace_bytes` - and
+        freed on return; boards beyond it are played through the same slices in the same launch.
+        Boards up to 8x8 with up to 8 tiles: ValueError otherwise."""
+        from . import _reach_cabi as rc
+        self._require_open()
+        if self.size > rc.REACH_MAX_SIZE or self.n_tiles > rc.REACH_MAX_TILES:
+            raise ValueError(f"solve_reachable() searches boards up to {rc.REACH_MAX_SIZE}x{rc.REACH_MAX_SIZE} with up to {rc.REACH_MAX_TILES} tiles; "
+                             f"{self.size}x{self.size} with {self.n_tiles} tiles is beyond that")
+        if not 0 <= int(max_depth) <= rc.REACH_MAX_DEPTH:
+            raise ValueError(f"max_depth must be 0..{rc.REACH_MAX_DEPTH}")
+        if not 1 <= int(capacity) <= rc.REACH_MAX_CAPACITY:
+            raise ValueError(f"capacity must be 1..{rc.REACH_MAX_CAPACITY}")
+        n = self.num_envs
+        moves = self._empty(n, torch.int16)
+        bits = self._empty(n, torch.uint8) if with_best else None
+        states = self._empty(n, torch.int32)
+        if n:
+            per_board = rc.workspace_bytes(self._dims, capacity, 1)
+            if int(workspace_bytes) < per_board:
+                raise ValueError(f"one board at capacity {int(capacity)} takes {per_board} bytes of workspace, above workspace_bytes = {int(workspace_bytes)}")
+            in_flight = rc.describe_reach(self._dims, max_depth, capacity, workspace_bytes)["boards_in_flight"]
+            ws = torch.empty(in_flight * per_board // 8, dtype=torch.int64, device=self.device)
+            cfg = rc.ReachCfg(int(max_depth), int(capacity), ws.data_ptr(), in_flight * per_board)
+            out = rc.ReachOut(_ptr(moves), _ptr(bits), _ptr(states))
+            self._call("ts_reach_solve", C.byref(self._dims), C.byref(self._state), C.byref(cfg), C.byref(out), binding=rc)
+        self._sync_if_host()
+        return ReachResult(moves, bits, states)
 
     # ------------------------------------------------------------------ distance-to-win tables (lib/libtiler_slider_table.so)
     def build_table(self, max_depth=252, max_bytes=4 << 30):
