@@ -50,9 +50,9 @@ struct UArgs {
   int32_t T, Tt, mc, max_steps, autoreset;
 };
 
-// The scattered observation stores.  Plain stores leave the touched lines dirty in the XCD's L2 until the end of the kernel;
-// -DTS_UPDATE_STORE_SC1 builds the agent-scope flavour (written through the L2) for the A/B of profiles/update_timing.md, and
-// -DTS_UPDATE_NO_PUT compiles them out: the time of everything else (profiles/update_requests.md).
+// The scattered observation stores.  A plain store leaves the touched line dirty in the XCD's L2 until capacity evicts it or
+// the kernel ends; an agent-scope store (sc1) is written through the L2 as it arrives.  Which one a kernel uses: kThrough below.
+// -DTS_UPDATE_NO_PUT compiles the stores out: the time of everything else (profiles/update_requests.md).
 // Who issues them.  The two-tile kernels: the four lanes of a quad, one slot each of one board's descriptor, board after board
 // (the file comment).  -DTS_UPDATE_LANE_PUT builds them as the eight-tile kernels are built: every lane stores its own board's
 // cells (profiles/update_requests.md, section 5, has the two side by side).
@@ -62,16 +62,67 @@ constexpr bool kQuadStore = false;
 #else
 constexpr bool kQuadStore = TMAX == 2;
 #endif
-template <class P>
+// Which flavour.  Written through where a quad stores AND a board's observation is 192 bytes, three whole 64-byte pieces
+// (float32 on 4x4 boards, uint8 on 8x8): the L1 merges a quad's stores per piece, a board's changed cells mostly share one
+// (1.02 pieces for 1.74 cells at cfg1) and no other board stores into it, so the written-through piece is the one fabric
+// write it was going to be anyway - and it leaves while the launch still runs instead of after its last wave.  Plain
+// everywhere else: where boards share pieces (float32 5x5, uint8 4x4 and 5x5: slower written through), on the 768-byte
+// float32 8x8 board (no gain) and where every lane stores its own board (the eight-tile kernels, -DTS_UPDATE_LANE_PUT: a
+// fabric write per changed float).  us per step, plain twice | written through twice, 1,048,576 boards where no number is
+// given (profiles/update_requests.md, section 6, has all rows):
+//   <4, 2, false>  17.92 17.82 | 16.49 16.74    524,288: 10.56 10.58 |  9.43  9.43    <8, 2, true>  524,288: 10.48 10.45 |  9.15  9.15
+//   <4, 2, true>   12.51 12.46 | 12.79 12.75    <5, 2, false>  37.56 37.58 | 37.76 37.59    <5, 2, true>  14.11 14.13 | 14.44 14.45
+//   <8, 2, false>  524,288: 19.73 19.70 | 19.89 19.72
+// -DTS_UPDATE_STORE_PLAIN gives every kernel the plain store back and -DTS_UPDATE_STORE_SC1 the written-through one.
+// Measured and not shipped, each replacing the rule above (section 6): -DTS_UPDATE_SC1_FIRST=K written through in the blocks
+// below gridDim.x / K and plain elsewhere, -DTS_UPDATE_SC1_LAST=K the same in the last gridDim.x / K blocks (uniform per block:
+// the two flavours of a store behind a scalar branch), -DTS_UPDATE_NT a nontemporal store.
+template <int S, int TMAX, bool U8>
+#if defined(TS_UPDATE_STORE_PLAIN)
+constexpr bool kThrough = false;
+#elif defined(TS_UPDATE_STORE_SC1)
+constexpr bool kThrough = true;
+#else
+constexpr bool kThrough = kQuadStore<TMAX> && S * S * 3 * (U8 ? 1 : 4) == 192;
+#endif
+#if defined(TS_UPDATE_SC1_FIRST) || defined(TS_UPDATE_SC1_LAST)
+__device__ __forceinline__ bool written_through() {
+#if defined(TS_UPDATE_SC1_FIRST)
+  return blockIdx.x < gridDim.x / (TS_UPDATE_SC1_FIRST);
+#else
+  return blockIdx.x >= gridDim.x - gridDim.x / (TS_UPDATE_SC1_LAST);
+#endif
+}
+#endif
+template <bool THROUGH, class P>
 __device__ __forceinline__ void put(P *dst, uint32_t v) {
 #if defined(TS_UPDATE_NO_PUT)
   (void)dst, (void)v;
-#elif defined(TS_UPDATE_STORE_SC1)
-  __hip_atomic_store(dst, (P)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store_* ... sc1
+#elif defined(TS_UPDATE_SC1_FIRST) || defined(TS_UPDATE_SC1_LAST)
+  if (written_through()) __hip_atomic_store(dst, (P)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *dst = (P)v;
+#elif defined(TS_UPDATE_NT)
+  __builtin_nontemporal_store((P)v, dst);  // global_store_* ... nt
 #else
-  *dst = (P)v;
+  if constexpr (THROUGH) __hip_atomic_store(dst, (P)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store_* ... sc1
+  else *dst = (P)v;
 #endif
 }
+
+// -DTS_UPDATE_TRACE=1: the timeline of one launch (tools/update_timeline.py).  Every wave stamps the 100 MHz clock at entry,
+// when its loads have returned (the trace waits for them there, all at once), before its first observation store and after
+// its last store instruction (=2: after that store is acknowledged), and its lane 0 writes the four stamps, the XCC id in the
+// top byte of the last, into an array of the code object that ts_update_trace_read copies out.  Never in the shipped build.
+#if defined(TS_UPDATE_TRACE)
+constexpr uint32_t kTraceWaves = 16384;  // cfg1: 4,096 blocks of four waves; waves past it are not recorded
+__device__ uint64_t g_trace[kTraceWaves * 4];
+__device__ __forceinline__ uint64_t stamp() {
+  asm volatile("" ::: "memory");
+  const uint64_t t = wall_clock64();
+  asm volatile("" ::: "memory");
+  return t;
+}
+#endif
 
 // Row `row` of a row-major [rows][N] array from board b0 on.  Everything here is uniform: the sum is scalar arithmetic, and
 // an access at(row_from(...), lane) takes the pointer from scalar registers and a 32-bit offset from the lane.  The empty
@@ -118,6 +169,9 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   const uint32_t ll = live ? tid : here - 1;
   const int T = FULL ? MT : a.T, Tt = FULL ? TMAX : a.Tt;  // 1 <= T <= MT, Tt <= TMAX
   const bool mc = a.mc != 0, autoreset = a.autoreset != 0;
+#if defined(TS_UPDATE_TRACE)
+  const uint64_t t_entry = stamp();
+#endif
 
   // ---- loads: all but the initial cells unconditional and issued before the first one is consumed ----
   M blk = at(row_from(a.blk, 0, N, b0), ll);
@@ -145,6 +199,10 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = at(row_from(a.init, min(t, T - 1), N, b0), ll);
   }
+#if defined(TS_UPDATE_TRACE)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint64_t t_loaded = stamp();
+#endif
 
   // ---- the step (environment.py:100-143), the order of k_small: done on entry, bad action, slide ----
   M tgm = 0, occ = 0;
@@ -230,6 +288,10 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   if constexpr (U8) block_obs = a.obs_u8 + b0 * (C * 3);
   else block_obs = a.obs + b0 * (C * 3);
   const uint32_t mine = tid * (uint32_t)(C * 3) + 1u;  // channel 1 of cell 0 of this board, from block_obs
+#if defined(TS_UPDATE_TRACE)
+  uint64_t t_store = 0;
+  if constexpr (!kQuadStore<TMAX>) t_store = stamp();  // the per-lane stores begin in the loop below
+#endif
   uint32_t word = 0;                                   // kQuadStore: what this board has to store (ts_quad.h)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -250,8 +312,8 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
       if constexpr (kQuadStore<TMAX>) {
         word |= ts::quad_word(ts::quad_slot(enters, c[t], nv), 2 * t) | ts::quad_word(ts::quad_slot(leaves, o[t], 0u), 2 * t + 1);
       } else {
-        if (enters) put(block_obs + (mine + 3u * c[t]), nv);
-        if (leaves) put(block_obs + (mine + 3u * o[t]), 0u);
+        if (enters) put<kThrough<S, TMAX, U8>>(block_obs + (mine + 3u * c[t]), nv);
+        if (leaves) put<kThrough<S, TMAX, U8>>(block_obs + (mine + 3u * o[t]), 0u);
       }
     }
   }
@@ -263,9 +325,12 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
     auto pass = [&](auto j) {  // j: a constant, the DPP control is an immediate
       const uint32_t theirs = (uint32_t)__builtin_amdgcn_mov_dpp((int)word, j * 0x55, 0xf, 0xf, true);
       const uint32_t slot = ts::quad_slot_of(theirs, my_slot);
-      if (ts::quad_present(slot)) put(block_obs + (quad + (uint32_t)(j * C * 3) + 3u * ts::quad_cell(slot)), ts::quad_value(slot));
+      if (ts::quad_present(slot)) put<kThrough<S, TMAX, U8>>(block_obs + (quad + (uint32_t)(j * C * 3) + 3u * ts::quad_cell(slot)), ts::quad_value(slot));
     };
     static_assert(ts::kQuadSlots == 4, "one pass per lane of a quad");
+#if defined(TS_UPDATE_TRACE)
+    t_store = stamp();
+#endif
     pass(std::integral_constant<int, 0>{}), pass(std::integral_constant<int, 1>{});
     pass(std::integral_constant<int, 2>{}), pass(std::integral_constant<int, 3>{});
   }
@@ -297,18 +362,43 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   }
 
   if (!live) return;
+  // -DTS_UPDATE_STATE_ALWAYS: the state rows under `live` alone - every store skipped here would write the byte that is there,
+  // and a row stored by all lanes of a wave is one whole 64-byte write (section 6: measured, not shipped).  A macro, not a
+  // constant or'ed into the conditions: that form reordered instructions of the default build.
+#if defined(TS_UPDATE_STATE_ALWAYS)
+#define TS_UPDATE_STATE_IF(cond) (true)
+#else
+#define TS_UPDATE_STATE_IF(cond) (cond)
+#endif
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     if (t < T) {
-      if (touched) at(row_from(a.pos, t, N, b0), tid) = (uint8_t)r[t];
-      if (r[t] != sh[t]) at(row_from(a.shown, t, N, b0), tid) = (uint8_t)r[t];
+      if (TS_UPDATE_STATE_IF(touched)) at(row_from(a.pos, t, N, b0), tid) = (uint8_t)r[t];
+      if (TS_UPDATE_STATE_IF(r[t] != sh[t])) at(row_from(a.shown, t, N, b0), tid) = (uint8_t)r[t];
     }
   }
-  if (touched) {
+  if (TS_UPDATE_STATE_IF(touched)) {
     at(row_from(a.step_count, 0, N, b0), tid) = sc;
     at(row_from(a.done, 0, N, b0), tid) = (uint8_t)done;
   }
   at(row_from(a.flags, 0, N, b0), tid) = (uint8_t)flags;
+#if defined(TS_UPDATE_KICK)
+  // -DTS_UPDATE_KICK=K: in every K-th group of eight blocks (eight: one block per XCD under the round-robin dealing, which
+  // only the speed depends on) lane 0 of wave 0 asks its L2 to write its dirty lines back and does not wait: the lines of
+  // earlier blocks leave while later ones still compute.  No store changes (section 6: measured, not shipped).
+  if (tid == 0 && (blockIdx.x >> 3) % (TS_UPDATE_KICK) == (TS_UPDATE_KICK) - 1) asm volatile("buffer_wbl2 sc1" ::: "memory");
+#endif
+#if defined(TS_UPDATE_TRACE)
+  if (TS_UPDATE_TRACE >= 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint64_t t_end = stamp();
+  uint32_t xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const uint32_t wave = blockIdx.x * (uint32_t)(kThreads / kWave) + tid / kWave;
+  if (tid % kWave == 0 && wave < kTraceWaves) {
+    uint64_t *w = g_trace + 4 * (size_t)wave;
+    w[0] = t_entry, w[1] = t_loaded, w[2] = t_store, w[3] = (t_end & 0x00ffffffffffffffull) | ((uint64_t)(xcc & 15u) << 56);
+  }
+#endif
 }
 
 // The kernel chooses its body once, on a uniform condition (full_body of _update_cabi.py says the same).  Only the two-tile
@@ -426,5 +516,15 @@ int32_t ts_step_update(const ts_dims *dims, const ts_state *st, const uint8_t *a
   hipLaunchKernelGGL(p.kernel, dim3(p.blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   return ts::finish_launch();
 }
+
+#if defined(TS_UPDATE_TRACE)
+// The last launch's stamps, four per wave, up to `words` 64-bit words of them; the number copied, or a negative TS_ERR_*.
+int64_t ts_update_trace_read(uint64_t *dst, int64_t words) {
+  if (!dst || words < 0) return TS_ERR_NULL;
+  const int64_t n = words < (int64_t)kTraceWaves * 4 ? words : (int64_t)kTraceWaves * 4;
+  if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_trace), (size_t)n * sizeof(uint64_t)) != hipSuccess) return TS_ERR_HIP;
+  return n;
+}
+#endif
 
 }  // extern "C"

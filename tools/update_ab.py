@@ -3,7 +3,7 @@
 VecTilerSliderEnv(obs_update="auto") allowed to step in place?
 
     python tools/update_ab.py [--log FILE] [--rounds 3] [--store plain|sc1|lane] [--define NAME[=VALUE] ...] [--library FILE]
-                              [--max-steps M] [--only cfg1_1m]
+                              [--max-steps M] [--obs-dtype float32|uint8] [--only cfg1_1m]
 
 Per shape two environments on the same levels (bench.py's LEVEL_SEED, multi colour, auto-reset, max_steps 2**30) and the same
 sixteen action buffers (ACTION_SEED): obs_update="inplace" (ts_step_update whatever the size of the buffer) and obs_update="full"
@@ -12,13 +12,17 @@ the two taking turns; the line gives every round, the medians and their ratio, a
 shape is timed the two environments are compared after 20 steps (observation, flags, cells): nothing is timed that computes
 something else.
 
---store sc1 loads a build of the library whose scattered observation stores are agent-scope stores (-DTS_UPDATE_STORE_SC1, built
-into build/variants/ through the guarded build on first use) instead of the shipped plain stores; --store lane one whose two-tile
-kernels store every board's cells from the board's own lane (-DTS_UPDATE_LANE_PUT) instead of from the four lanes of its quad.
+--store sc1 loads a build of the library whose scattered observation stores are agent-scope stores in every kernel
+(-DTS_UPDATE_STORE_SC1, built into build/variants/ through the guarded build on first use) - the shipped build has them in the
+two two-tile kernels whose board is 192 bytes of observation and plain stores in the others, and --define TS_UPDATE_STORE_PLAIN
+builds plain stores everywhere; --store lane a build whose two-tile kernels store every board's cells from the board's own lane
+(-DTS_UPDATE_LANE_PUT, plain stores) instead of from the four lanes of its quad.
 --define NAME[=VALUE] (repeatable) does the same for any other build-time knob of csrc/ts_update.hip - the ablations of
 profiles/update_requests.md are -DTS_UPDATE_NO_PUT (the observation stores compiled out) and -DTS_UPDATE_ARITH_TWICE (the slides
-computed twice) - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps with a build of the library made
-elsewhere (the parent commit's, say).  --max-steps 7 times episodes that end every seventh step, so that most waves reset.
+computed twice), the write-back variants of its section 6 -DTS_UPDATE_SC1_FIRST=K, -DTS_UPDATE_SC1_LAST=K, -DTS_UPDATE_NT,
+-DTS_UPDATE_KICK=K and -DTS_UPDATE_STATE_ALWAYS - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps
+with a build of the library made elsewhere (the parent commit's, say).  --max-steps 7 times episodes that end every seventh
+step, so that most waves reset; --obs-dtype uint8 times both environments with the uint8 observation.
 profiles/update_ab.log is where a run of this script belongs; run it under `timeout`.
 """
 import argparse
@@ -44,6 +48,7 @@ SHAPES = {
     "cfg1_4m": (4, 2, 2, 4 << 20),
     "cfg1_16m": (4, 2, 2, 16 << 20),
     "8x8_4_512k": (8, 4, 6, 524288),
+    "8x8_2_512k": (8, 2, 6, 524288),
     "5x5_2_1m": (5, 2, 3, 1 << 20),
 }
 
@@ -58,6 +63,7 @@ def main():
     ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]", help="-D knob of csrc/ts_update.hip; repeatable")
     ap.add_argument("--library", default=None, help="a build of libtiler_slider_update.so to step with instead of the shipped one")
     ap.add_argument("--max-steps", type=int, default=2**30)
+    ap.add_argument("--obs-dtype", choices=("float32", "uint8"), default="float32")
     ap.add_argument("--check", choices=("all", "state"), default=None,
                     help="what the two environments must agree on before a shape is timed; state: flags and cells only, the default "
                          "with -DTS_UPDATE_NO_PUT, whose build leaves the observation alone")
@@ -98,7 +104,7 @@ def main():
     stream = torch.cuda.current_stream(dev).cuda_stream
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     say(f"# tools/update_ab.py --store {args.store}{''.join(' --define ' + d for d in args.define)}"
-        f"{' --max-steps %d' % args.max_steps if args.max_steps != 2**30 else ''}: {args.steps} timed steps after {args.warmup} warm-up steps, HIP events, us per step; "
+        f"{' --max-steps %d' % args.max_steps if args.max_steps != 2**30 else ''}{' --obs-dtype uint8' if args.obs_dtype == 'uint8' else ''}: {args.steps} timed steps after {args.warmup} warm-up steps, HIP events, us per step; "
         f"{torch.cuda.get_device_name(dev)}")
     say(f"# library: {os.path.relpath(_update_cabi.LIB_PATH, ROOT)}")
     say("# shape            boards  obs MiB  kernel (in place)              in place, rounds        full, rounds            in place  full    full / in place  auto")
@@ -116,10 +122,11 @@ def main():
     names = args.only.split(",") if args.only else list(SHAPES)
     for name in names:
         S, T, K, n = SHAPES[name]
-        kw = dict(size=S, num_tiles=T, num_obstacles=K, seed=LEVEL_SEED, multi_color=True, max_steps=args.max_steps, device=dev, auto_reset=True)
+        kw = dict(size=S, num_tiles=T, num_obstacles=K, seed=LEVEL_SEED, multi_color=True, max_steps=args.max_steps, device=dev, auto_reset=True,
+                  obs_dtype=args.obs_dtype)
         inplace = VecTilerSliderEnv.random(n, obs_update="inplace", **kw)
         full = VecTilerSliderEnv.random(n, obs_update="full", **kw)
-        auto_says = "in place" if VecTilerSliderEnv.in_place_pays(inplace._obs.numel() * 4, n, T) else "full"
+        auto_says = "in place" if VecTilerSliderEnv.in_place_pays(inplace._obs.numel() * inplace._obs.element_size(), n, T) else "full"
         ring = []
         for i in range(16):
             a = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -144,8 +151,8 @@ def main():
             us_in.append(timed(inplace, ring))
             us_full.append(timed(full, ring))
         m_in, m_full = statistics.median(us_in), statistics.median(us_full)
-        kernel = _cabi.describe_launch(inplace._dims, _cabi.OP_STEP, _cabi.OUT_OBS)["name"]
-        say(f"{name:<16} {n:>9} {inplace._obs.numel() * 4 / 2**20:>8.1f}  {kernel:<29}  {' '.join(f'{u:7.2f}' for u in us_in):<23} "
+        kernel = _cabi.describe_launch(inplace._dims, _cabi.OP_STEP, _cabi.OUT_OBS_U8 if args.obs_dtype == "uint8" else _cabi.OUT_OBS)["name"]
+        say(f"{name:<16} {n:>9} {inplace._obs.numel() * inplace._obs.element_size() / 2**20:>8.1f}  {kernel:<29}  {' '.join(f'{u:7.2f}' for u in us_in):<23} "
             f"{' '.join(f'{u:7.2f}' for u in us_full):<23} {m_in:7.2f} {m_full:7.2f}  {m_full / m_in:8.2f}x         {auto_says}")
         del inplace, full, ring
         torch.cuda.empty_cache()
