@@ -10,8 +10,8 @@ trajectory_logits() lib/libtiler_slider_train.so, the first trajectory_outputs()
 trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the first actor_critic_loss() or trajectory_loss()
 lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so,
 the first place_at_distance() lib/libtiler_slider_starts.so, the first build_policy_table(), walk_actions() or score_policy()
-lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, and each fails loudly if its library is
-missing (no CPU fallback).
+lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, the first build_reach_table() or
+lookup() of a ReachTable lib/libtiler_slider_rtable.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -22,6 +22,8 @@ from ._ptable_cabi import build_library as build_ptable_library
 from ._reach_cabi import SOLVE_FULL
 from ._reach_cabi import build_library as build_reach_library
 from ._rollout_cabi import build_library as build_rollout_library
+from ._rtable_cabi import SOLVE_ABSENT
+from ._rtable_cabi import build_library as build_rtable_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
 from ._search_cabi import build_library as build_search_library
 from ._starts_cabi import build_library as build_starts_library
@@ -44,7 +46,7 @@ from .ptable import PolicyScore, PolicyTable
 from .render import TextRender
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
-from .vec_env import DistanceTable, ReachResult, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
+from .vec_env import DistanceTable, ReachResult, ReachTable, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
 __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "ImageLoader", "TextRender",
@@ -58,4 +60,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "LossInfo", "actor_critic_loss", "actor_critic_loss_grads", "build_loss_library",
            "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library",
            "PolicyTable", "PolicyScore", "build_ptable_library",
-           "ReachResult", "SOLVE_FULL", "build_reach_library"]
+           "ReachResult", "SOLVE_FULL", "build_reach_library",
+           "ReachTable", "SOLVE_ABSENT", "build_rtable_library"]

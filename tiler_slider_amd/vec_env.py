@@ -147,6 +147,52 @@ class ReachResult:
         return f"ReachResult(moves, best, bits, states: [{self.moves.shape[0]}])"
 
 
+class ReachTable:
+    """What VecTilerSliderEnv.build_reach_table() returns (include/tiler_slider_rtable.h), on the device: `table` int64 [L, slots], a
+    hash table per level - a slot is 0 or bit 63 | the entry << 48 | the key, so an occupied slot is negative; `count` int32 [L],
+    the states the level holds, or SOLVE_FULL; `root_moves` int16 [L], the optimum from the root; `deepest` int32 [L], the largest
+    distance of the row; `capacity`, `max_depth`, `root` ("init" or "pos") and the shape it was built for - lookups refuse an
+    environment of another.  Which slot a state lies in differs from build to build: compare tables by entries()."""
+
+    def __init__(self, table, count, root_moves, deepest, capacity, size, n_tiles, n_targets, multi_color, max_depth, root):
+        self.table, self.count, self.root_moves, self.deepest = table, count, root_moves, deepest
+        self.capacity, self.max_depth, self.root = int(capacity), int(max_depth), root
+        self.size, self.n_tiles, self.n_targets, self.multi_color = int(size), int(n_tiles), int(n_targets), bool(multi_color)
+        self._full = None
+
+    @property
+    def shape_key(self):
+        return (self.size, self.n_tiles, self.n_targets, self.multi_color)
+
+    @property
+    def slots(self):
+        return self.table.shape[1]
+
+    @property
+    def full(self):
+        """bool [L]: the level reaches more than `capacity` states; every lookup into it answers SOLVE_FULL."""
+        if self._full is None:
+            from ._reach_cabi import SOLVE_FULL
+            self._full = self.count == SOLVE_FULL
+        return self._full
+
+    def entries(self, level):
+        """(keys int64 [count] ascending, entries uint8 [count]) of one level: key = sum_t cell_t * (size * size) ** t, entry
+        1 .. 252, TABLE_DEEP or TABLE_NONE.  Both empty for a FULL level: its row holds nothing to use."""
+        row = self.table[level]
+        if int(self.count[level]) < 0:
+            row = row[:0]
+        row = row[row < 0]
+        keys, order = torch.sort(row & ((1 << 48) - 1))
+        return keys, ((row >> 48) & 0xFF).to(torch.uint8)[order]
+
+    def __len__(self):
+        return self.table.shape[0]
+
+    def __repr__(self):
+        return f"ReachTable({len(self)} levels x {self.slots} slots, capacity {self.capacity}, root {self.root!r})"
+
+
 class Rollout:
     """What VecTilerSliderEnv.rollout() returns: the reductions and logs of include/tiler_slider_rollout.h (ts_rollout_out) as
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
@@ -995,7 +1041,8 @@ class VecTilerSliderEnv:
     def lookup(self, table, rows=None):
         """(moves int16 [N], best bool [N, 4]) of the boards as they stand, read from `table` (build_table): what solve() returns
         wherever the table is complete.  `rows` int32 [N]: board n reads table row rows[n] (default: row n) - the caller's promise
-        that the row was built for that board's level."""
+        that the row was built for that board's level.  `table` may be a ReachTable (build_reach_table): moves can then be
+        SOLVE_FULL or SOLVE_ABSENT as well."""
         moves, bits = self.lookup_bits(table, rows)
         return moves, _bit_columns(bits)
 
@@ -1019,12 +1066,80 @@ class VecTilerSliderEnv:
     def _lookup(self, table, rows, want_moves, want_best, want_action):
         from . import _table_cabi as tc
         self._require_open()
+        if isinstance(table, ReachTable):
+            return self._lookup_reach(table, rows, want_moves, want_best, want_action)
         dist, n_rows, rows = self._check_table(table, rows)
         moves = self._empty(self.num_envs, torch.int16) if want_moves else None
         best = self._empty(self.num_envs, torch.uint8) if want_best else None
         action = self._empty(self.num_envs, torch.uint8) if want_action else None
         self._call("ts_table_lookup", C.byref(self._dims), C.byref(self._state), _ptr(dist), n_rows, _ptr(rows), _ptr(moves), _ptr(best),
                    _ptr(action), binding=tc)
+        self._sync_if_host()
+        return moves, best, action
+
+    # ------------------------------------------------------------------ reachable distance tables (lib/libtiler_slider_rtable.so)
+    def build_reach_table(self, capacity=4096, max_depth=252, root="init", max_bytes=4 << 30, workspace_bytes=1 << 30):
+        """build_table() for boards whose index space is beyond it: solve every board's LEVEL once over the placements play can
+        REACH from its root (include/tiler_slider_rtable.h: ts_rtable_build, one launch) - a ReachTable, one hash table of
+        pow2ceil(2 * capacity) 64-bit slots per level.  root="init": the level's initial cells, so the table stays right through
+        reset() and auto-reset; root="pos": the cells as they stand.  A level that reaches more than `capacity` states is FULL
+        (`.full`).  lookup(), lookup_bits() and expert_actions_from() take the table as they take build_table()'s: moves is 0 on
+        a won board, the least number of moves, SOLVE_NONE, SOLVE_DEPTH (not resolved within `max_depth` rounds), SOLVE_FULL for
+        a FULL level, or SOLVE_ABSENT where the level's table does not hold the board's placement - play from the root never
+        gets there.  Reads the level and the root only and writes no state.
+        The table takes N * slots * 8 bytes: above `max_bytes` this raises - build the table on an environment of the DISTINCT
+        levels and pass `rows=` to the lookups.  The workspace is allocated here - one slice per level in flight, at most 1,024
+        levels and at most `workspace_bytes` - and freed on return.  Boards up to 8x8 with up to 8 tiles: ValueError otherwise."""
+        from . import _reach_cabi as rc, _rtable_cabi as xc, _table_cabi as tc
+        self._require_open()
+        self._require_reach_table_shape(rc)
+        if not 0 <= int(max_depth) <= tc.TABLE_MAX_DEPTH:
+            raise ValueError(f"max_depth must be 0..{tc.TABLE_MAX_DEPTH}")
+        if not 1 <= int(capacity) <= rc.REACH_MAX_CAPACITY:
+            raise ValueError(f"capacity must be 1..{rc.REACH_MAX_CAPACITY}")
+        if root not in xc.ROOTS:
+            raise ValueError(f"root must be one of {sorted(xc.ROOTS)}, got {root!r}")
+        n, slots = self.num_envs, xc.slots(capacity)
+        nbytes = n * slots * 8
+        if nbytes > int(max_bytes):
+            raise ValueError(f"a table of {n} boards x {slots} slots takes {nbytes} bytes, above max_bytes = {int(max_bytes)}: "
+                             "build it on an environment of the distinct levels and pass rows= to lookup() / expert_actions_from()")
+        table = torch.empty((n, slots), dtype=torch.int64, device=self.device)
+        count = self._empty(n, torch.int32)
+        root_moves = self._empty(n, torch.int16)
+        deepest = self._empty(n, torch.int32)
+        if n:
+            per_level = xc.workspace_bytes(self._dims, capacity, 1)
+            if int(workspace_bytes) < per_level:
+                raise ValueError(f"one level at capacity {int(capacity)} takes {per_level} bytes of workspace, above workspace_bytes = {int(workspace_bytes)}")
+            in_flight = xc.describe_rtable_build(self._dims, max_depth, capacity, workspace_bytes)["levels_in_flight"]
+            ws = torch.empty(in_flight * per_level // 8, dtype=torch.int64, device=self.device)
+            cfg = xc.RtableCfg(int(max_depth), int(capacity), xc.ROOTS[root], ws.data_ptr(), in_flight * per_level)
+            out = xc.RtableOut(_ptr(table), _ptr(count), _ptr(root_moves), _ptr(deepest))
+            self._call("ts_rtable_build", C.byref(self._dims), C.byref(self._state), C.byref(cfg), C.byref(out), binding=xc)
+        self._sync_if_host()
+        return ReachTable(table, count, root_moves, deepest, capacity, self.size, self.n_tiles, self.n_targets, self.multi_color, max_depth, root)
+
+    def _require_reach_table_shape(self, rc):
+        if self.size > rc.REACH_MAX_SIZE or self.n_tiles > rc.REACH_MAX_TILES:
+            raise ValueError(f"reachable distance tables cover boards up to {rc.REACH_MAX_SIZE}x{rc.REACH_MAX_SIZE} with up to {rc.REACH_MAX_TILES} tiles; "
+                             f"{self.size}x{self.size} with {self.n_tiles} tiles is beyond that")
+
+    def _lookup_reach(self, table, rows, want_moves, want_best, want_action):
+        from . import _reach_cabi as rc, _rtable_cabi as xc
+        self._require_reach_table_shape(rc)
+        mine = (self.size, self.n_tiles, self.n_targets, self.multi_color)
+        if table.shape_key != mine:
+            raise ValueError(f"the table was built for (size, tiles, targets, multi colour) = {table.shape_key}, the environment is {mine}")
+        if table.table.device != self.device:
+            raise ValueError(f"the table lives on {table.table.device}, the environment on {self.device}")
+        n_rows = len(table)
+        rows = self._check_rows(rows, n_rows)
+        moves = self._empty(self.num_envs, torch.int16) if want_moves else None
+        best = self._empty(self.num_envs, torch.uint8) if want_best else None
+        action = self._empty(self.num_envs, torch.uint8) if want_action else None
+        self._call("ts_rtable_lookup", C.byref(self._dims), C.byref(self._state), _ptr(table.table), table.slots, _ptr(table.count), n_rows,
+                   _ptr(rows), _ptr(moves), _ptr(best), _ptr(action), binding=xc)
         self._sync_if_host()
         return moves, best, action
 
@@ -1270,6 +1385,10 @@ class VecTilerSliderEnv:
         if table.dist.device != self.device:
             raise ValueError(f"the table lives on {table.dist.device}, the environment on {self.device}")
         n_rows = table.dist.shape[0]
+        return table.dist, n_rows, self._check_rows(rows, n_rows)
+
+    def _check_rows(self, rows, n_rows):
+        """The rows of a lookup in a table of n_rows rows, validated: contiguous int32 on the device, or None."""
         if rows is None:
             if n_rows != self.num_envs:
                 raise ValueError(f"the table has {n_rows} rows for {self.num_envs} boards: pass rows= (int32 [{self.num_envs}])")
@@ -1283,7 +1402,7 @@ class VecTilerSliderEnv:
             rows = rows.to(device=self.device, dtype=torch.int32).contiguous()
             if self.strict and self.num_envs and bool(((rows < 0) | (rows >= n_rows)).any()):  # a sync, as step()'s strict check
                 raise ValueError(f"rows outside the table's 0..{n_rows - 1}")
-        return table.dist, n_rows, rows
+        return rows
 
     # ------------------------------------------------------------------ internals
     def _info(self):
