@@ -5,9 +5,20 @@ Imports neither torch nor the libraries at import time."""
 import numpy as np
 
 import rollout_reference as rref
+from table_harness import _OCC_SHAPES
 
 MAX_DEPTH = 252
 ALL, DONE = 0, 1
+
+# kernel name -> (S, T): one occupancy case per kernel of the starts library, on the shapes of the table library's cases.
+# tests/test_gpu_starts.py runs them at OCC_BLOCKS one-wave blocks and more, tests/test_starts_cpu.py pins the names to the code object
+OCCUPANCY_CASES = {f"k_starts_place<{_S}>": (_S, _T) for _S, (_T, _K) in _OCC_SHAPES.items()}
+OCC_BLOCKS, OCC_ROWS = 4096, 128
+
+
+def occupancy_boards(boards_per_block):
+    """Boards that fill OCC_BLOCKS blocks and leave the last one ragged where a block holds more than one board."""
+    return OCC_BLOCKS * boards_per_block + boards_per_block // 2 + 1
 
 
 def place(table, C, T, n_boards, lo=1, hi=MAX_DEPTH, band=None, rows=None, selected=None, seed=0, step_index=0, board_offset=0):

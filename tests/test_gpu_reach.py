@@ -35,6 +35,14 @@ def _seeded(S, T, K, n):
     return _oracle().generate_mt19937(S, T, T, K, np.arange(n, dtype=np.uint32))
 
 
+def _drawn(S, T, K, mc, n):
+    """The first n levels of the occupancy case of size S (tests/reach_cases.py) where (T, K) is its shape, else the seeded ones."""
+    import reach_cases as cases
+    if (T, K) != cases.SHAPES[S][:2]:
+        return _seeded(S, T, K, n)
+    return tuple(np.ascontiguousarray(a[:, :n]) for a in cases.levels(_oracle(), S, mc))
+
+
 @functools.lru_cache(maxsize=None)
 def _walked(S, T, K, L, n):
     """(blk, init, tgt): the level of seed i with its targets moved to where L moves of ts_fill_actions' stream leave the tiles.
@@ -115,11 +123,13 @@ def _same(got, want, ctx):
 
 
 # ---------------------------------------------------------------------------------------------------- against ts_solve itself
-@pytest.mark.parametrize("S,T,K,mc,n", ((4, 2, 2, False, 300), (3, 4, 1, False, 300), (4, 4, 2, True, 64), (4, 2, 2, True, 300)))
+@pytest.mark.parametrize("S,T,K,mc,n", ((4, 2, 2, False, 300), (3, 4, 1, False, 300), (4, 4, 2, True, 64), (4, 2, 2, True, 300),
+                                         (3, 5, 1, False, 64), (3, 5, 1, True, 64)))
 def test_equals_ts_solve_where_both_apply(torch_cuda, S, T, K, mc, n):
-    """capacity = the index space: never FULL, so moves and best are ts_solve's, bit for bit, at full depth and cut short."""
+    """capacity = the index space: never FULL, so moves and best are ts_solve's, bit for bit, at full depth and cut short.  3x3 with
+    five tiles is the one shape ts_solve takes whose keys split into two halves, by a division that is no shift."""
     from tiler_slider_amd import SOLVE_FULL
-    blk, init, tgt = _seeded(S, T, K, n)
+    blk, init, tgt = _drawn(S, T, K, mc, n)
     env = _env(S, mc, blk, init, tgt)
     for depth in (64, 5, 0):
         moves, bits = env.solve_bits(depth)

@@ -186,14 +186,17 @@ def _check(S, mc, blk, init, tgt, ref, ctx, **build):
 
 
 # ---------------------------------------------------------------------------------------------------- against the existing libraries
-@pytest.mark.parametrize("S,T,K,mc,n", ((4, 2, 2, False, 64), (4, 2, 2, True, 64), (3, 4, 1, False, 32), (4, 4, 2, True, 8)))
+@pytest.mark.parametrize("S,T,K,mc,n", ((4, 2, 2, False, 64), (4, 2, 2, True, 64), (3, 4, 1, False, 32), (4, 4, 2, True, 8),
+                                         (3, 5, 1, False, 64), (3, 5, 1, True, 64)))
 def test_equals_the_dense_table_and_the_hashed_solver_where_all_apply(torch_cuda, S, T, K, mc, n):
     """capacity = the index space: never FULL.  Every state of R reads what ts_table_lookup reads from a complete build_table(),
-    and root_moves is ts_reach_solve's moves."""
+    and root_moves is ts_reach_solve's moves.  3x3 with five tiles is the one shape the dense tables take whose keys split into two
+    halves, by a division that is no shift."""
     import rtable_reference as rt
+    from test_gpu_reach import _drawn
     from tiler_slider_amd import TABLE_MAX_DEPTH
     torch = torch_cuda
-    blk, init, tgt = _seeded(S, T, K, n)
+    blk, init, tgt = _drawn(S, T, K, mc, n)
     space = (S * S) ** T
     ref = rt.build(_oracle(), S, mc, blk, tgt, init, 252, space)
     assert (ref.count >= 0).all() and (ref.count > 1).sum() >= n // 2

@@ -13,7 +13,7 @@ from table_harness import GUARD, GUARD_BYTE, guarded as _guarded, payload as _pa
 pytestmark = pytest.mark.gpu
 
 SEED = 0xF00DFACE12345678      # above 2^63: the seed is unsigned
-SHAPES = ((1, 1), (3, 1), (3, 2), (5, 2), (7, 1), (4, 2), (8, 1), (4, 3), (8, 2), (3, 5))      # states 1 .. 59,049, mostly odd
+SHAPES = ((1, 1), (2, 2), (3, 1), (3, 2), (5, 2), (6, 2), (7, 1), (4, 2), (8, 1), (4, 3), (8, 2), (3, 5))      # states 1 .. 59,049, mostly odd; every size
 BOARDS = (1, 63, 257)
 BANDS = ((0, 0), (1, 252), (2, 4), (5, 3), "per board")
 
@@ -151,6 +151,48 @@ def test_the_scan_at_every_alignment(torch_cuda, S, T):
                 np.testing.assert_array_equal(_payload(tbuf, np.uint8, (shift + n_rows * states,))[shift:], tab.reshape(-1))
     assert placed_total > 0 and unplaced_total > 0
     assert 0 in counts_seen and states in counts_seen and (states <= 2 or len(counts_seen) > 3)      # from nothing to the whole row
+
+
+@pytest.mark.parametrize("name", sorted(sref.OCCUPANCY_CASES))
+def test_every_compiled_starts_kernel_at_occupancy(torch_cuda, name):
+    """Every kernel of the starts library at 4,096 one-wave blocks and more, the last one ragged where a block holds several
+    boards: a made-up table of 128 rows read through rows=, a band per board, every byte of state, outputs and guards against the
+    yardstick's."""
+    torch = torch_cuda
+    from tiler_slider_amd import _cabi, _starts_cabi as sc
+    dev = torch.device("cuda", torch.cuda.current_device())
+    S, T = sref.OCCUPANCY_CASES[name]
+    C_, states = S * S, (S * S) ** T
+    rng = np.random.default_rng(0x0CC + S)
+    per_block = sc.describe_starts_place(_cabi.Dims(1, S, T, T, 0, 100, 0))["boards_per_block"]
+    N = sref.occupancy_boards(per_block)
+    dims = _cabi.Dims(N, S, T, T, 0, 100, 0)
+    d = sc.describe_starts_place(dims)
+    assert d["name"] == name and d["threads_per_block"] == 64 and d["blocks"] >= sref.OCC_BLOCKS and (per_block == 1 or N % per_block != 0)
+    n_rows = sref.OCC_ROWS
+    tab = _made_up_table(rng, n_rows, states, 1, 252)
+    rows = rng.integers(0, n_rows, N).astype(np.int32)
+    rows[rng.integers(0, N, 8)] = np.array([-1, n_rows] * 4, np.int32)
+    band = rng.integers(0, 256, (2, N)).astype(np.uint8)
+    band[1, ::2] = np.maximum(band[1, ::2], band[0, ::2])     # half of the bands are not empty
+    band[1, ::5] = rng.integers(253, 256, len(band[1, ::5]))  # bytes above the largest distance
+    ref = sref.place(tab, C_, T, N, band=band, rows=rows, seed=SEED, step_index=5, board_offset=1000)
+    placed, counts = int(ref["placed"].sum()), set(ref["count"].tolist())
+    print(f"{name}: {N} boards in {d['blocks']} blocks of {per_block}, {placed} placed, {N - placed} not, counts {min(counts)} .. {max(counts)} of {states}")
+    assert placed >= 64 and N - placed >= 64 and 0 in counts and (states <= 2 or len(counts) > 3)
+    tbuf = _guarded(torch, dev, tab)
+    before = _state(rng, C_, T, N)
+    before["band"], before["rows"] = band, rows
+    arena = _Arena(before)
+    buf = torch.from_numpy(arena.build(before)).to(dev)
+    kw = dict(lo=1, hi=252, where=sc.ALL, write_pos=1, write_init=1, seed=SEED, step_index=5, board_offset=1000)
+    assert _raw_call(torch, dev, dims, arena, buf, tbuf.data_ptr() + GUARD, n_rows, kw, True, True) == 0
+    after = dict(before)
+    after["pos"], after["init"], after["step_count"], after["done"] = sref.apply(ref, before["pos"], before["init"], before["step_count"], before["done"], 1, 1)
+    after["count"], after["dist"], after["deepest"] = ref["count"], ref["dist"], ref["deepest"]
+    bad = arena.differing(buf.cpu().numpy(), arena.build(after))
+    assert not bad, (name, bad)
+    np.testing.assert_array_equal(_payload(tbuf, np.uint8, (n_rows * states,)), tab.reshape(-1))
 
 
 def test_starts_done_places_exactly_the_boards_that_are_done(torch_cuda):

@@ -12,6 +12,8 @@ from conftest import GOLDEN_DIR, ROOT
 
 # size, tiles, obstacles, multi colour: the rows of DESIGN.md section 11 (tests/test_gpu_solver.py: ROWS)
 ROWS = ((4, 2, 2, False), (4, 2, 2, True), (5, 2, 3, False), (5, 3, 3, True), (6, 3, 6, False), (8, 2, 10, True), (3, 4, 1, False), (4, 4, 2, True))
+# 3x3 with five tiles, 59,049 placements: more than four tiles, C4 = 81^2 no power of two, and the dense yardstick still takes it
+LONG_ROWS = ((3, 5, 1, False), (3, 5, 1, True))
 
 
 def test_abi_version_and_constants_are_the_headers():
@@ -146,12 +148,50 @@ def test_the_kernels_use_no_scratch_no_float_and_plain_vector_memory_only():
         assert floats == 0 and scratch == 0 and barriers > 0 and cas > 0, (k, floats, scratch, barriers, cas)
 
 
-@pytest.mark.parametrize("S,T,K,mc", ROWS)
+def test_occupancy_cases_name_exactly_the_compiled_reach_kernels():
+    """tests/test_gpu_reach_occupancy.py runs one case per kernel on a full grid: its case table (tests/reach_cases.py) is the code
+    object's list, no kernel without a case and no case without a kernel; the library names that kernel for the case's dims and
+    plans the grid the GPU test relies on - 1,024 blocks, a slice each, for a batch of 1,024 + 61 boards."""
+    import reach_cases as cases
+    from tiler_slider_amd import _reach_cabi as rc
+    assert sorted(cases.REACH_CASES) == _kernel_names(rc.LIB_PATH)
+    assert len(cases.REACH_CASES) == rc.MIN_KERNELS == 8
+    for name, (S, T, K) in cases.REACH_CASES.items():
+        assert name == f"k_reach<{S}>" and (T, K) == cases.SHAPES[S][:2] and T + K <= S * S and (T > 4 or S * S <= 4)
+        for mc in (0, 1):
+            for depth in (64, 3):
+                d = rc.describe_reach(_dims(S, T, mc, cases.N_BUILD), depth, cases.CAPACITY)
+                assert (d["name"], d["blocks"], d["boards_in_flight"], d["threads_per_block"]) == (name, cases.GRID, cases.GRID, 256), d
+    assert cases.N_BUILD > cases.GRID and cases.N_BUILD % cases.GRID == 61
+
+
+@pytest.mark.parametrize("S", range(1, 9))
+def test_occupancy_cases_are_not_degenerate(oracle, S):
+    """The conditions tests/reach_cases.py sets on the yardstick's answer hold for the levels it draws: boards that can be won,
+    boards that cannot and boards that run out of their budget in every case from 3x3 up, in both colour modes."""
+    import reach_cases as cases
+    import reach_reference as reach
+    seen = set()
+    for mc in (False, True):
+        blk, init, tgt = cases.levels(oracle, S, mc)
+        assert blk.shape[1] == init.shape[1] == tgt.shape[1] == cases.DISTINCT and init.shape[0] == cases.SHAPES[S][0]
+        s = cases.check_reach(S, reach.solve(oracle, S, mc, blk, tgt, init, 64, cases.CAPACITY))
+        seen |= {k for k in ("won", "solved", "none") if s[k]}
+        assert S == 1 or (s["won"] and s["solved"] + s["none"]), s
+    assert "won" in seen and seen & {"solved", "none"}
+
+
+@pytest.mark.parametrize("S,T,K,mc", ROWS + LONG_ROWS)
 def test_yardstick_equals_the_dense_one_where_the_budget_is_the_index_space(oracle, S, T, K, mc):
     """capacity = (S * S) ** T can never be exceeded: moves and best of tests/solver_reference.py, at full depth and cut short."""
     import reach_reference as reach
     import solver_reference as dense
-    blk, init, tgt = oracle.generate_mt19937(S, T, T, K, np.arange(64, dtype=np.uint32))
+    if (S, T, K, mc) in LONG_ROWS:
+        import reach_cases as cases
+        assert (T, K) == cases.SHAPES[S][:2]
+        blk, init, tgt = (np.ascontiguousarray(a[:, :64]) for a in cases.levels(oracle, S, mc))
+    else:
+        blk, init, tgt = oracle.generate_mt19937(S, T, T, K, np.arange(64, dtype=np.uint32))
     space = (S * S) ** T
     for depth in (64, 3, 0):
         want = dense.solve(oracle, S, mc, blk, tgt, init, depth)

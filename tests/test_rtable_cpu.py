@@ -13,6 +13,8 @@ from conftest import ROOT
 
 # size, tiles, obstacles, seeds: shapes the dense tables take as well
 DENSE = ((3, 2, 1, 64), (4, 2, 2, 64), (4, 4, 2, 8))
+# 3x3 with five tiles, 59,049 placements: more than four tiles, C4 = 81^2 no power of two, and the dense yardstick still takes it
+LONG = (3, 5, 1, 64)
 
 
 def test_abi_version_and_constants_are_the_headers():
@@ -189,14 +191,54 @@ def test_the_kernels_use_no_scratch_no_float_and_plain_vector_memory_only():
         assert floats == 0 and scratch == 0 and barriers == 0 and atomics == 0, (k, floats, scratch, barriers, atomics)
 
 
-@pytest.mark.parametrize("S,T,K,n", DENSE)
+def test_occupancy_cases_name_exactly_the_compiled_rtable_kernels():
+    """tests/test_gpu_reach_occupancy.py runs one case per kernel - the builds on a full grid, the lookups at 4,096 waves -: its
+    case table (tests/reach_cases.py) is the code object's list, no kernel without a case and no case without a kernel; the
+    library names the build kernel for the case's dims and plans the grid the GPU test relies on, 1,024 blocks for 1,024 + 61
+    levels."""
+    import reach_cases as cases
+    from tiler_slider_amd import _rtable_cabi as xc
+    assert sorted(cases.RTABLE_CASES) == _kernel_names(xc.LIB_PATH)
+    assert len(cases.RTABLE_CASES) == xc.MIN_KERNELS == 16
+    for name, (S, T, K) in cases.RTABLE_CASES.items():
+        what = "build" if "build" in name else "lookup"
+        assert name == f"k_rtable_{what}<{S}>" and (T, K) == cases.SHAPES[S][:2] and T + K <= S * S and (T > 4 or S * S <= 4)
+        for mc in (0, 1):
+            for depth in (252, 3):
+                for root in (0, 1):
+                    d = xc.describe_rtable_build(_dims(S, T, mc, cases.N_BUILD), depth, cases.CAPACITY, root=root)
+                    assert (d["name"], d["blocks"], d["levels_in_flight"], d["threads_per_block"]) == (f"k_rtable_build<{S}>", cases.GRID, cases.GRID, 256), d
+    assert cases.N_LOOKUP % 64 != 0 and -(-cases.N_LOOKUP // 64) >= 4096   # one board per lane: at least 4,096 waves, a ragged last one
+
+
+@pytest.mark.parametrize("S", range(1, 9))
+def test_occupancy_cases_are_not_degenerate(oracle, S):
+    """The conditions tests/reach_cases.py sets on the yardstick's answer hold for the levels it draws, in both colour modes: large
+    levels that are built, FULL levels, won roots, spread root distances, entries of both kinds - and keys beyond 2^32 from 6x6."""
+    import reach_cases as cases
+    import rtable_reference as rt
+    won = not_won = 0
+    for mc in (False, True):
+        blk, init, tgt = cases.levels(oracle, S, mc)
+        s = cases.check_rtable(S, rt.build(oracle, S, mc, blk, tgt, init, 252, cases.CAPACITY))
+        won, not_won = won + s["won"], not_won + cases.DISTINCT - s["won"]
+        assert S == 1 or (s["won"] and s["won"] < cases.DISTINCT), s
+    assert won and not_won
+
+
+@pytest.mark.parametrize("S,T,K,n", DENSE + (LONG,))
 @pytest.mark.parametrize("mc", (False, True))
 def test_yardstick_equals_the_dense_one_on_every_state_it_reaches(oracle, S, T, K, n, mc):
     """Every state of R holds the dense table's entry (a path to the win stays inside R), no state of R is won or invalid there,
     the successors are the dense table's, and deepest / root_moves / count follow from the row."""
     import rtable_reference as rt
     import table_reference as dense
-    blk, init, tgt = oracle.generate_mt19937(S, T, T, K, np.arange(n, dtype=np.uint32))
+    if (S, T, K, n) == LONG:
+        import reach_cases as cases
+        assert (T, K) == cases.SHAPES[S][:2]
+        blk, init, tgt = (np.ascontiguousarray(a[:, :n]) for a in cases.levels(oracle, S, mc))
+    else:
+        blk, init, tgt = oracle.generate_mt19937(S, T, T, K, np.arange(n, dtype=np.uint32))
     exact = dense.exact(oracle, S, mc, blk, tgt, T)
     assert exact[exact < dense.UNREACHABLE].max() <= dense.MAX_DEPTH
     full = dense.cut(exact)

@@ -173,6 +173,23 @@ def test_describe_plans_lanes_and_passes_and_names_exactly_the_compiled_kernels(
     assert (nothing["form"], nothing["blocks"], nothing["name"], nothing["states"], nothing["passes"]) == (sc.FORM_NONE, 0, "", 256, 0)
 
 
+def test_occupancy_cases_name_exactly_the_compiled_starts_kernels():
+    """tests/test_gpu_starts.py runs one case per kernel at 4,096 one-wave blocks and more: its case table
+    (tests/starts_reference.py) is the code object's list, no kernel without a case and no case without a kernel; the library
+    names that kernel for the case's dims and plans the grid the GPU test relies on, with a ragged last block where a block holds
+    several boards."""
+    assert sorted(sref.OCCUPANCY_CASES) == _kernel_names(sc.LIB_PATH)
+    assert len(sref.OCCUPANCY_CASES) == sc.MIN_KERNELS == 8
+    for name, (S, T) in sref.OCCUPANCY_CASES.items():
+        assert name == f"k_starts_place<{S}>" and (S * S) ** T <= 65536
+        per_block = sc.describe_starts_place(_dims(S, T, 0, 1))["boards_per_block"]
+        n = sref.occupancy_boards(per_block)
+        d = sc.describe_starts_place(_dims(S, T, 0, n))
+        assert (d["name"], d["form"], d["threads_per_block"], d["boards_per_block"]) == (name, sc.FORM_WAVE, 64, per_block), d
+        assert d["blocks"] >= sref.OCC_BLOCKS and (per_block == 1 or n % per_block != 0), d
+    assert {sc.describe_starts_place(_dims(S, T, 0, 9))["boards_per_block"] for S, T in sref.OCCUPANCY_CASES.values()} >= {1, 4, 8, 64}
+
+
 def test_the_starts_kernels_use_no_scratch_no_lds_and_no_agprs():
     kernels = _kernel_metadata(sc.LIB_PATH)
     assert len(kernels) == len([k for k in kernels if "k_starts_place" in k["name"]]) == sc.MIN_KERNELS
