@@ -85,6 +85,70 @@ constexpr bool kThrough = true;
 #else
 constexpr bool kThrough = kQuadStore<TMAX> && S * S * 3 * (U8 ? 1 : 4) == 192;
 #endif
+// A priority schedule per wave.  The SIMD picks the next instruction by priority, then by age, and every wave runs at priority
+// 0: a wave that has just entered - one latency-bound round trip of loads away from having work - loses every pick to the
+// arithmetic and the store instructions of older waves.  Where kLoadsFirst holds, a wave raises its priority (s_setprio)
+// behind its wave-uniform early return, issues its loads - in a resetting wave the initial cells too - and drops to 0 again
+// where the two paths of the reset branch have rejoined: at any moment the waves in their load phase stand above the waves in
+// their store phase.  Raise and drop are asm statements with a memory clobber, so no load or store moves across them.
+// Which kernels: those with a measured row on which both readings with the schedule lie below both without it - the two-tile
+// kernels of 4x4, 5x5 and 8x8 boards, both observation types, and <8, 8, false>.  No other kernel has a row; they keep their
+// code.  us per step, without twice | with twice, 1,048,576 boards where no number is given (profiles/update_requests.md,
+// section 7, has all rows, the bench line and the timeline):
+//   <4, 2, false>  16.58 16.51 | 16.07 18.80 (one whole process in the slow state section 6 met with both trees; six more
+//                  pairs: 16.49 .. 16.71 | 16.02 .. 16.12)    524,288: 9.42 9.42 | 9.26 9.26    786,432: 13.47 13.48 | 12.64 12.63
+//   <4, 2, true>   12.45 12.41 | 12.34 12.27    <5, 2, false>  37.99 37.96 | 36.46 37.01    <5, 2, true>  14.13 14.12 | 13.98 13.94
+//   <8, 2, true>   524,288:  9.16  9.16 |  8.79  8.81    <8, 2, false>  524,288: 19.66 19.66 | 19.24 19.43
+//   <8, 8, false>  524,288: 45.88 45.50 | 45.11 45.03
+// -DTS_UPDATE_PRIO_OFF: false everywhere (the parent's code, instruction for instruction); -DTS_UPDATE_PRIO_ALL: true in all 32
+// kernels.  -DTS_UPDATE_PRIO_LEVEL=1|2|3 the raised level (no difference between them: 16.12, 16.12, 16.11); -DTS_UPDATE_PRIO_UNTIL=
+// issued|loaded|store where the drop stands: behind the last load instruction, behind the wait for all loads (16.12: in
+// auto-reset mode a wave has waited for its done latches by then in either form), or in front of the first observation
+// store, so that the step runs raised as well (16.74 to 16.81: slower than no schedule); -DTS_UPDATE_PRIO_STORES the control:
+// loads at 0, the raise in front of the first observation store and no drop (16.59 to 16.68: the parent's time).
+template <int S, int TMAX, bool U8>
+#if defined(TS_UPDATE_PRIO_OFF)
+constexpr bool kLoadsFirst = false;
+#elif defined(TS_UPDATE_PRIO_ALL)
+constexpr bool kLoadsFirst = true;
+#else
+constexpr bool kLoadsFirst = (TMAX == 2 && (S == 4 || S == 5 || S == 8)) || (S == 8 && TMAX == 8 && !U8);
+#endif
+#if defined(TS_UPDATE_PRIO_LEVEL)
+constexpr int kPrioLevel = TS_UPDATE_PRIO_LEVEL;
+#else
+constexpr int kPrioLevel = 1;
+#endif
+static_assert(kPrioLevel >= 1 && kPrioLevel <= 3, "s_setprio takes 0 .. 3, and 0 is where a wave starts");
+enum PrioUntil { kUntil_issued, kUntil_loaded, kUntil_store };
+#if defined(TS_UPDATE_PRIO_UNTIL)
+#define TS_PRIO_PASTE_(a, b) a##b
+#define TS_PRIO_PASTE(a, b) TS_PRIO_PASTE_(a, b)
+constexpr PrioUntil kPrioUntil = TS_PRIO_PASTE(kUntil_, TS_UPDATE_PRIO_UNTIL);  // another word does not compile
+#else
+constexpr PrioUntil kPrioUntil = kUntil_issued;
+#endif
+#if defined(TS_UPDATE_PRIO_STORES)
+constexpr bool kPrioStores = true;
+#else
+constexpr bool kPrioStores = false;
+#endif
+// The memory clobber holds loads and stores on their side.  The drop behind the loads is pinned against the arithmetic as well
+// (a scheduling barrier on either side emits nothing): left alone, the scheduler lifts the first consumers of the loaded values,
+// and with them the wait for every load, above it - and the drop behind the issue becomes a drop behind the return.
+template <int LEVEL, bool PINNED = false>
+__device__ __forceinline__ void set_prio() {
+  if constexpr (PINNED) __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_setprio %0" ::"n"(LEVEL) : "memory");
+  if constexpr (PINNED) __builtin_amdgcn_sched_barrier(0);
+}
+// In front of a wave's first observation store: the late drop, or the control's raise.
+template <bool PRIO>
+__device__ __forceinline__ void prio_at_first_store() {
+  if constexpr (PRIO && kPrioStores) set_prio<kPrioLevel>();
+  else if constexpr (PRIO && kPrioUntil == kUntil_store) set_prio<0>();
+}
+
 #if defined(TS_UPDATE_SC1_FIRST) || defined(TS_UPDATE_SC1_LAST)
 __device__ __forceinline__ bool written_through() {
 #if defined(TS_UPDATE_SC1_FIRST)
@@ -164,6 +228,8 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   const uint32_t tid = threadIdx.x;
   const uint32_t here = (uint32_t)min(N - b0, (int64_t)kThreads);  // boards of this block, 1 .. 256
   if ((tid & ~(uint32_t)(kWave - 1)) >= here) return;              // wave-uniform
+  constexpr bool kPrio = kLoadsFirst<S, TMAX, U8>;
+  if constexpr (kPrio && !kPrioStores) set_prio<kPrioLevel>();  // this wave's loads before whatever older waves have to issue
   // lanes past the batch play a copy of the LAST board and write nothing
   const bool live = tid < here;
   const uint32_t ll = live ? tid : here - 1;
@@ -198,6 +264,10 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   if (autoreset && __ballot(done != 0) != 0) {  // wave-uniform
 #pragma unroll
     for (int t = 0; t < MT; ++t) in[t] = at(row_from(a.init, min(t, T - 1), N, b0), ll);
+  }
+  if constexpr (kPrio && !kPrioStores && kPrioUntil != kUntil_store) {
+    if constexpr (kPrioUntil == kUntil_loaded) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    set_prio<0, kPrioUntil == kUntil_issued>();  // every load is issued, the initial cells of a resetting wave among them
   }
 #if defined(TS_UPDATE_TRACE)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -292,6 +362,7 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
   uint64_t t_store = 0;
   if constexpr (!kQuadStore<TMAX>) t_store = stamp();  // the per-lane stores begin in the loop below
 #endif
+  if constexpr (!kQuadStore<TMAX>) prio_at_first_store<kPrio>();
   uint32_t word = 0;                                   // kQuadStore: what this board has to store (ts_quad.h)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
@@ -331,6 +402,7 @@ __device__ __forceinline__ void step_update_body(const UArgs &a) {
 #if defined(TS_UPDATE_TRACE)
     t_store = stamp();
 #endif
+    prio_at_first_store<kPrio>();
     pass(std::integral_constant<int, 0>{}), pass(std::integral_constant<int, 1>{});
     pass(std::integral_constant<int, 2>{}), pass(std::integral_constant<int, 3>{});
   }

@@ -20,7 +20,9 @@ builds plain stores everywhere; --store lane a build whose two-tile kernels stor
 --define NAME[=VALUE] (repeatable) does the same for any other build-time knob of csrc/ts_update.hip - the ablations of
 profiles/update_requests.md are -DTS_UPDATE_NO_PUT (the observation stores compiled out) and -DTS_UPDATE_ARITH_TWICE (the slides
 computed twice), the write-back variants of its section 6 -DTS_UPDATE_SC1_FIRST=K, -DTS_UPDATE_SC1_LAST=K, -DTS_UPDATE_NT,
--DTS_UPDATE_KICK=K and -DTS_UPDATE_STATE_ALWAYS - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps
+-DTS_UPDATE_KICK=K and -DTS_UPDATE_STATE_ALWAYS, the priority schedule of its section 7 -DTS_UPDATE_PRIO_OFF (in no kernel: the
+parent's code), -DTS_UPDATE_PRIO_ALL (in all 32; the shipped build has it in seven), -DTS_UPDATE_PRIO_LEVEL=1|2|3,
+-DTS_UPDATE_PRIO_UNTIL=issued|loaded|store and the control -DTS_UPDATE_PRIO_STORES - into build/variants/libtiler_slider_update_<names>.so; --library FILE steps
 with a build of the library made elsewhere (the parent commit's, say).  --max-steps 7 times episodes that end every seventh
 step, so that most waves reset; --obs-dtype uint8 times both environments with the uint8 observation.
 profiles/update_ab.log is where a run of this script belongs; run it under `timeout`.

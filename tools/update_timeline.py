@@ -3,6 +3,7 @@
 store the observation and when they are through (csrc/ts_update.hip, -DTS_UPDATE_TRACE; profiles/update_requests.md, section 6).
 
     timeout 300 python tools/update_timeline.py [--log profiles/update_timeline.log] [--shape cfg1_1m] [--steps 60] [--resident 8192]
+                                                [--define NAME[=VALUE] ...]
 
 One process, tools/update_pmc_target.py's environment (update_ab.py's levels and action buffers, multi colour, auto-reset,
 obs_update="inplace"): a reset and --steps steps with the shipped library, with the -DTS_UPDATE_TRACE=1 build and with the
@@ -11,8 +12,15 @@ variant), the last 50 steps of each between two HIP events.  A traced build has 
 and its lane 0 write the stamps into an array of the code object; ts_update_trace_read copies the last launch's out.  TRACE=2
 waits for the wave's stores to be acknowledged before the last stamp: its store stall less TRACE=1's is that wait.
 
-Waves are ranked by their entry stamp and cut into rounds of --resident (256 CUs x 4 SIMDs x 8 waves of 28 registers).  All times
-are us from the first wave's entry; a stamp is 10 ns, so medians of a few ticks are coarse.  Run it under `timeout`."""
+--define NAME[=VALUE] adds a knob to the two traced builds (build/variants/libtiler_slider_update_trace<level>_<names>.so):
+TS_UPDATE_PRIO_OFF gives the timeline without the priority schedule (profiles/update_timeline_prio_off.log), TS_UPDATE_PRIO_ALL
+the timeline with it for a shape whose kernel does not ship it.
+
+Waves are ranked by their entry stamp and cut into rounds of --resident (256 CUs x 4 SIMDs x 8 waves of 28 registers).  Per
+round the median, the 10th and 90th percentile and the maximum of load wait, compute and store stall, then their means and the
+mean residency (entry to end); then per us the waves that enter, begin to store and end in it, and the waves resident - in a
+slot - at its start.  All times are us from the first wave's entry; a stamp is 10 ns, so medians of a few ticks are coarse.
+Run it under `timeout`."""
 import argparse
 import ctypes as C
 import os
@@ -34,6 +42,16 @@ def spread(xs):
     return f"{statistics.median(xs) * TICK_US:6.2f} [{q(0.1):5.2f} .. {q(0.9):5.2f}] {xs[-1] * TICK_US:6.2f}"
 
 
+def mean_us(xs):
+    return statistics.fmean(xs) * TICK_US
+
+
+def resident_at(rows, t0, n_bins):
+    """Waves resident at t0 + b us, b = 0 .. n_bins - 1: entered at or before that tick and not yet ended."""
+    ticks_per_us = round(1 / TICK_US)
+    return [sum(1 for r in rows if r[0] <= t0 + b * ticks_per_us < r[3]) for b in range(n_bins)]
+
+
 def report(say, rows, resident, us_step):
     """rows: (entry, loaded, store, end, xcc) per recorded wave, in ticks."""
     rows.sort()
@@ -46,6 +64,12 @@ def report(say, rows, resident, us_step):
         part = rows[k:k + resident]
         say(f"  {k // resident:>5} {len(part):>6}  {(part[0][0] - t0) * TICK_US:6.2f} .. {(part[-1][0] - t0) * TICK_US:6.2f}      "
             f"{spread([r[1] - r[0] for r in part])}   {spread([r[2] - r[1] for r in part])}   {spread([r[3] - r[2] for r in part])}")
+    say("  round  mean: load wait  compute  store stall  residency (entry to end)")
+    for k in range(0, len(rows), resident):
+        part = rows[k:k + resident]
+        say(f"  {k // resident:>5}        {mean_us([r[1] - r[0] for r in part]):9.2f} {mean_us([r[2] - r[1] for r in part]):8.2f} "
+            f"{mean_us([r[3] - r[2] for r in part]):12.2f} {mean_us([r[3] - r[0] for r in part]):10.2f}")
+    say(f"  mean residency of all waves, entry to end: {mean_us([r[3] - r[0] for r in rows]):.2f} us")
     say(f"  observation stores issue from {(min(r[2] for r in rows) - t0) * TICK_US:.2f} to {(max(r[2] for r in rows) - t0) * TICK_US:.2f} us; "
         f"waves end from {(first_end - t0) * TICK_US:.2f} to {(end - t0) * TICK_US:.2f} us")
     span = (end - t0) * TICK_US
@@ -56,6 +80,7 @@ def report(say, rows, resident, us_step):
         for r in rows:
             hist[min(len(hist) - 1, int((r[col] - t0) * TICK_US))] += 1
         say(f"  {name} " + " ".join(f"{h:>5}" for h in hist))
+    say("  resident" + " ".join(f"{h:>5}" for h in resident_at(rows, t0, int(span) + 1)) + "   (waves in a slot at the start of each us)")
     by_xcc = {}
     for r in rows:
         by_xcc.setdefault(r[4], []).append(r)
@@ -69,6 +94,8 @@ def main():
     ap.add_argument("--shape", default="cfg1_1m", choices=sorted(update_ab.SHAPES))
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--resident", type=int, default=8192)
+    ap.add_argument("--define", action="append", default=[], metavar="NAME[=VALUE]",
+                    help="-D knob of csrc/ts_update.hip for the two traced builds (TS_UPDATE_PRIO_OFF: the timeline without the priority schedule); repeatable")
     args = ap.parse_args()
     if args.steps < 51:
         ap.error("--steps: at least 51 (the last 50 are timed)")
@@ -77,11 +104,13 @@ def main():
 
     shipped = uc.LIB_PATH
     libraries = [("shipped", shipped)]
+    tag = "".join("_" + d.replace("TS_UPDATE_", "").replace("=", "").lower() for d in args.define)
     for level in (1, 2):
-        variant = os.path.join(ROOT, "build", "variants", f"libtiler_slider_update_trace{level}.so")
+        variant = os.path.join(ROOT, "build", "variants", f"libtiler_slider_update_trace{level}{tag}.so")
         if not os.path.exists(variant) or os.path.getmtime(variant) < os.path.getmtime(uc.SRC):
-            _cabi.compile_guarded(uc.SRC, variant, defines=(f"-DTS_UPDATE_TRACE={level}",), work=os.path.dirname(variant), min_kernels=uc.MIN_KERNELS)
-        libraries.append((f"TS_UPDATE_TRACE={level}", variant))
+            _cabi.compile_guarded(uc.SRC, variant, defines=(f"-DTS_UPDATE_TRACE={level}", *("-D" + d for d in args.define)),
+                                  work=os.path.dirname(variant), min_kernels=uc.MIN_KERNELS)
+        libraries.append((" ".join([f"TS_UPDATE_TRACE={level}", *args.define]), variant))
 
     lines = []
 
