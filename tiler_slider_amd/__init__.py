@@ -11,7 +11,8 @@ trajectory_returns() or trajectory_labels() lib/libtiler_slider_targets.so, the 
 lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_optim.so,
 the first place_at_distance() lib/libtiler_slider_starts.so, the first build_policy_table(), walk_actions() or score_policy()
 lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, the first build_reach_table() or
-lookup() of a ReachTable lib/libtiler_slider_rtable.so, and each fails loudly if its library is missing (no CPU fallback).
+lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy="reach") or trajectory_labels() of a ReachTable
+lib/libtiler_slider_rexpert.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -21,6 +22,7 @@ from ._policy_cabi import build_library as build_policy_library
 from ._ptable_cabi import build_library as build_ptable_library
 from ._reach_cabi import SOLVE_FULL
 from ._reach_cabi import build_library as build_reach_library
+from ._rexpert_cabi import build_library as build_rexpert_library
 from ._rollout_cabi import build_library as build_rollout_library
 from ._rtable_cabi import SOLVE_ABSENT
 from ._rtable_cabi import build_library as build_rtable_library
@@ -61,4 +63,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library",
            "PolicyTable", "PolicyScore", "build_ptable_library",
            "ReachResult", "SOLVE_FULL", "build_reach_library",
-           "ReachTable", "SOLVE_ABSENT", "build_rtable_library"]
+           "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library"]

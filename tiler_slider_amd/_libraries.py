@@ -6,8 +6,8 @@ byte what was tested and measured (section 23 says what a 
 An entry is the binding module itself, so nothing a binding knows is restated here; __graft_entry__.build() and the CPU tests
 iterate over this tuple.
 """
-from . import (_ac_cabi, _cabi, _loss_cabi, _optim_cabi, _policy_cabi, _ptable_cabi, _reach_cabi, _rollout_cabi, _rtable_cabi,
-               _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi)
+from . import (_ac_cabi, _cabi, _loss_cabi, _optim_cabi, _policy_cabi, _ptable_cabi, _reach_cabi, _rexpert_cabi, _rollout_cabi,
+               _rtable_cabi, _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi)
 
 LIBRARIES = (_cabi, _search_cabi, _table_cabi, _rollout_cabi, _policy_cabi, _train_cabi, _targets_cabi, _ac_cabi, _update_cabi,
              _loss_cabi, _optim_cabi, _starts_cabi)
@@ -20,7 +20,7 @@ LATER = (_ptable_cabi,)
 # Every library since then is an entry here: built by build_added after build_later, reported on lines that begin "added: built",
 # checked by tests/test_libraries_added_cpu.py, which iterates over this tuple and pins no list of names - the next library is
 # one more entry, not a fourth tuple.
-ADDED = (_reach_cabi, _rtable_cabi)
+ADDED = (_reach_cabi, _rtable_cabi, _rexpert_cabi)
 
 
 def name(binding):

@@ -1125,8 +1125,11 @@ class VecTilerSliderEnv:
             raise ValueError(f"reachable distance tables cover boards up to {rc.REACH_MAX_SIZE}x{rc.REACH_MAX_SIZE} with up to {rc.REACH_MAX_TILES} tiles; "
                              f"{self.size}x{self.size} with {self.n_tiles} tiles is beyond that")
 
-    def _lookup_reach(self, table, rows, want_moves, want_best, want_action):
-        from . import _reach_cabi as rc, _rtable_cabi as xc
+    def _check_reach_table(self, table, rows):
+        """The ReachTable and rows of a lookup, validated: (n_rows, rows as contiguous int32 on the device or None)."""
+        from . import _reach_cabi as rc
+        if not isinstance(table, ReachTable):
+            raise TypeError(f"table must be a ReachTable (build_reach_table()), got {type(table)}")
         self._require_reach_table_shape(rc)
         mine = (self.size, self.n_tiles, self.n_targets, self.multi_color)
         if table.shape_key != mine:
@@ -1134,7 +1137,11 @@ class VecTilerSliderEnv:
         if table.table.device != self.device:
             raise ValueError(f"the table lives on {table.table.device}, the environment on {self.device}")
         n_rows = len(table)
-        rows = self._check_rows(rows, n_rows)
+        return n_rows, self._check_rows(rows, n_rows)
+
+    def _lookup_reach(self, table, rows, want_moves, want_best, want_action):
+        from . import _rtable_cabi as xc
+        n_rows, rows = self._check_reach_table(table, rows)
         moves = self._empty(self.num_envs, torch.int16) if want_moves else None
         best = self._empty(self.num_envs, torch.uint8) if want_best else None
         action = self._empty(self.num_envs, torch.uint8) if want_action else None
@@ -1194,6 +1201,9 @@ class VecTilerSliderEnv:
                  "random": the stream of ts_fill_actions(seed, board_offset, step_index + k)
                  "table":  the expert move of `table` (build_table(); `rows` as in lookup()), replaced by the random draw with
                            probability `epsilon` and wherever the expert has no move
+                 "reach":  the same on a ReachTable (build_reach_table()), for shapes beyond the tables' index space: still one
+                           launch (include/tiler_slider_rexpert.h: ts_rexpert_rollout); no move also where the row is FULL or
+                           does not hold the board's placement
           stats=True: wins, finished, first_win, win_moves, reward_sum, flags (False: none; or an iterable of those names)
           log: any of "act", "flags", "pos" - the per-step logs act_log, flags_log uint8 [steps, N], pos_log [steps, T, N] - and
                  "start": Rollout.start_pos, a copy of the cells before the launch (what trajectory_labels() and a reward on
@@ -1203,6 +1213,9 @@ class VecTilerSliderEnv:
                  boards stand; the environment is left untouched.
         Returns a Rollout.  Boards up to 8x8 with at most 8 tiles and 8 targets; "table" also needs the tables' index space
         (size * size) ** n_tiles <= 65536: ValueError otherwise."""
+        if policy == "reach":  # lib/libtiler_slider_rexpert.so: the rollout library is not consulted
+            from .rexpert import rollout_reach
+            return rollout_reach(self, steps, table, rows, epsilon, seed, step_index, board_offset, stats, log, advance)
         from . import _rollout_cabi as rc
         self._require_open()
         if not self._started:
@@ -1354,7 +1367,11 @@ class VecTilerSliderEnv:
         board a Rollout visited - row k is the answer on the board step k was chosen on (start_pos, then pos_log[k - 1]) - in ONE
         launch (include/tiler_slider_targets.h: ts_traj_labels).  `action` is a cross_entropy target wherever it is not 255 (the
         expert has no move: the board is won, cannot be won, or its row lies outside the table).  The rollout needs log
-        ("start", "pos"); table and rows as lookup().  No state is touched."""
+        ("start", "pos"); table and rows as lookup().  No state is touched.  `table` may be a ReachTable (build_reach_table()):
+        still one launch (include/tiler_slider_rexpert.h: ts_rexpert_labels), and moves can be SOLVE_FULL or SOLVE_ABSENT as well."""
+        if isinstance(table, ReachTable):
+            from .rexpert import trajectory_labels_reach
+            return trajectory_labels_reach(self, rollout, table, rows)
         from .targets import trajectory_labels
         return trajectory_labels(self, rollout, table, rows)
 
@@ -1377,7 +1394,8 @@ class VecTilerSliderEnv:
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
         from . import _table_cabi as tc
         if not isinstance(table, DistanceTable):
-            raise TypeError(f"table must be a DistanceTable (build_table()), got {type(table)}")
+            raise TypeError(f"table must be a DistanceTable (build_table()), got {type(table)}"
+                            + ('; a ReachTable is played by rollout(policy="reach") and read by lookup() and trajectory_labels()' if isinstance(table, ReachTable) else ""))
         states = self._table_states(tc)
         mine = (self.size, self.n_tiles, self.n_targets, self.multi_color)
         if table.shape_key != mine or table.dist.shape[1] != states:
