@@ -12,7 +12,8 @@ lib/libtiler_slider_loss.so, the first FusedAdam.step() lib/libtiler_slider_opti
 the first place_at_distance() lib/libtiler_slider_starts.so, the first build_policy_table(), walk_actions() or score_policy()
 lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, the first build_reach_table() or
 lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy="reach") or trajectory_labels() of a ReachTable
-lib/libtiler_slider_rexpert.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_rexpert.so, the first build_reach_index() or place_at_distance() of a ReachIndex
+lib/libtiler_slider_rstarts.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -24,6 +25,7 @@ from ._reach_cabi import SOLVE_FULL
 from ._reach_cabi import build_library as build_reach_library
 from ._rexpert_cabi import build_library as build_rexpert_library
 from ._rollout_cabi import build_library as build_rollout_library
+from ._rstarts_cabi import build_library as build_rstarts_library
 from ._rtable_cabi import SOLVE_ABSENT
 from ._rtable_cabi import build_library as build_rtable_library
 from ._search_cabi import SOLVE_DEPTH, SOLVE_NONE
@@ -46,6 +48,7 @@ from .pipelined import PipelinedTilerSliderEnv
 from .policy import MlpPolicy
 from .ptable import PolicyScore, PolicyTable
 from .render import TextRender
+from .rstarts import ReachIndex
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
 from .vec_env import DistanceTable, ReachResult, ReachTable, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
@@ -63,4 +66,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "FusedAdam", "build_optim_library", "StartInfo", "build_starts_library",
            "PolicyTable", "PolicyScore", "build_ptable_library",
            "ReachResult", "SOLVE_FULL", "build_reach_library",
-           "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library"]
+           "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library",
+           "ReachIndex", "build_rstarts_library"]

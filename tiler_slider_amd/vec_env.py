@@ -1127,6 +1127,11 @@ class VecTilerSliderEnv:
 
     def _check_reach_table(self, table, rows):
         """The ReachTable and rows of a lookup, validated: (n_rows, rows as contiguous int32 on the device or None)."""
+        n_rows = self._check_reach_table_itself(table)
+        return n_rows, self._check_rows(rows, n_rows)
+
+    def _check_reach_table_itself(self, table):
+        """A ReachTable of this environment's shape and device: its number of levels."""
         from . import _reach_cabi as rc
         if not isinstance(table, ReachTable):
             raise TypeError(f"table must be a ReachTable (build_reach_table()), got {type(table)}")
@@ -1136,8 +1141,7 @@ class VecTilerSliderEnv:
             raise ValueError(f"the table was built for (size, tiles, targets, multi colour) = {table.shape_key}, the environment is {mine}")
         if table.table.device != self.device:
             raise ValueError(f"the table lives on {table.table.device}, the environment on {self.device}")
-        n_rows = len(table)
-        return n_rows, self._check_rows(rows, n_rows)
+        return len(table)
 
     def _lookup_reach(self, table, rows, want_moves, want_best, want_action):
         from . import _rtable_cabi as xc
@@ -1149,6 +1153,17 @@ class VecTilerSliderEnv:
                    _ptr(rows), _ptr(moves), _ptr(best), _ptr(action), binding=xc)
         self._sync_if_host()
         return moves, best, action
+
+    # ------------------------------------------------------------------ reach-table curricula (lib/libtiler_slider_rstarts.so)
+    def build_reach_index(self, table, max_bytes=4 << 30):
+        """What place_at_distance() reads of a ReachTable: every level's states sorted by (distance, key), and for every
+        distance where its states begin (include/tiler_slider_rstarts.h: ts_rstarts_index, one launch) - a ReachIndex of
+        `sorted` int64 [L, capacity] and `first` int32 [L, 256].  A FULL level has an empty index: no board is placed from it.
+        The index is a function of what the table holds, not of where it holds it: two builds of one table give the same bits.
+        It takes L * (capacity * 8 + 1024) bytes: above `max_bytes` this raises - build the table on an environment of the
+        DISTINCT levels and pass `rows=` to place_at_distance().  Reads the table only and writes no state."""
+        from .rstarts import build_reach_index
+        return build_reach_index(self, table, max_bytes)
 
     # ------------------------------------------------------------------ curriculum starts (lib/libtiler_slider_starts.so)
     def place_at_distance(self, table, min_moves=1, max_moves=None, rows=None, band=None, seed=0, step_index=0, board_offset=0,
@@ -1162,11 +1177,17 @@ class VecTilerSliderEnv:
         again.  only_done=True places only the boards that are done - fresh starts between strict-mode rollouts.  A placed
         board gets step_count 0 and done False, and with set_initial=True the placement becomes its level's initial cells:
         reset() and the auto-reset return there.  The observation buffer shows the new cells afterwards (the full write of
-        reset()); the last step's `info` is left as it is."""
+        reset()); the last step's `info` is left as it is.
+        `table` may be a ReachIndex (build_reach_index) instead: the same call on the shapes beyond build_table()
+        (include/tiler_slider_rstarts.h: ts_rstarts_place), with one difference - a reach table stores no won placement, so
+        distance 0 never matches."""
         from . import _starts_cabi as sc
         from ._table_cabi import TABLE_MAX_DEPTH
+        from .rstarts import ReachIndex, place_reach
         self._require_open()
-        dist_table, n_rows, rows = self._check_table(table, rows)
+        reach = isinstance(table, ReachIndex)
+        if not reach:
+            dist_table, n_rows, rows = self._check_table(table, rows, 'place_at_distance() takes what build_reach_index() makes of it')
         N = self.num_envs
         lo, hi = int(min_moves), TABLE_MAX_DEPTH if max_moves is None else int(max_moves)
         if not (0 <= lo <= TABLE_MAX_DEPTH and 0 <= hi <= TABLE_MAX_DEPTH):
@@ -1179,8 +1200,11 @@ class VecTilerSliderEnv:
         cfg = sc.StartsCfg(lo, hi, _ptr(band), sc.DONE if only_done else sc.ALL, 1, 1 if set_initial else 0, 0,
                            int(seed) & (2 ** 64 - 1), int(step_index), int(board_offset))
         out = sc.StartsOut(_ptr(count), _ptr(dist), _ptr(deepest))
-        self._call("ts_starts_place", C.byref(self._dims), C.byref(self._state), _ptr(dist_table), n_rows, _ptr(rows), C.byref(cfg),
-                   C.byref(out), binding=sc)
+        if reach:
+            place_reach(self, table, rows, cfg, out)
+        else:
+            self._call("ts_starts_place", C.byref(self._dims), C.byref(self._state), _ptr(dist_table), n_rows, _ptr(rows), C.byref(cfg),
+                       C.byref(out), binding=sc)
         if self._obs is not None:
             self.encode(out=self._obs)  # the full write reset() makes, and _sync_shown(): an environment that steps in place stays right
         self._sync_if_host()
@@ -1390,12 +1414,12 @@ class VecTilerSliderEnv:
         from .loss import trajectory_loss
         return trajectory_loss(self, logits, rollout, targets, values, labels, clip, value_coef, entropy_coef, normalize_adv)
 
-    def _check_table(self, table, rows):
+    def _check_table(self, table, rows, reach_advice='a ReachTable is played by rollout(policy="reach") and read by lookup() and trajectory_labels()'):
         """The table and rows of a lookup, validated: (dist, n_rows, rows as contiguous int32 on the device or None)."""
         from . import _table_cabi as tc
         if not isinstance(table, DistanceTable):
             raise TypeError(f"table must be a DistanceTable (build_table()), got {type(table)}"
-                            + ('; a ReachTable is played by rollout(policy="reach") and read by lookup() and trajectory_labels()' if isinstance(table, ReachTable) else ""))
+                            + (f"; {reach_advice}" if isinstance(table, ReachTable) else ""))
         states = self._table_states(tc)
         mine = (self.size, self.n_tiles, self.n_targets, self.multi_color)
         if table.shape_key != mine or table.dist.shape[1] != states:
