@@ -13,7 +13,8 @@ the first place_at_distance() lib/libtiler_slider_starts.so, the first build_pol
 lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_reach.so, the first build_reach_table() or
 lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy="reach") or trajectory_labels() of a ReachTable
 lib/libtiler_slider_rexpert.so, the first build_reach_index() or place_at_distance() of a ReachIndex
-lib/libtiler_slider_rstarts.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_rstarts.so, the first build_policy_table(), walk_actions() or score_policy() of a ReachTable
+lib/libtiler_slider_rptable.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -25,6 +26,7 @@ from ._reach_cabi import SOLVE_FULL
 from ._reach_cabi import build_library as build_reach_library
 from ._rexpert_cabi import build_library as build_rexpert_library
 from ._rollout_cabi import build_library as build_rollout_library
+from ._rptable_cabi import build_library as build_rptable_library
 from ._rstarts_cabi import build_library as build_rstarts_library
 from ._rtable_cabi import SOLVE_ABSENT
 from ._rtable_cabi import build_library as build_rtable_library
@@ -48,6 +50,7 @@ from .pipelined import PipelinedTilerSliderEnv
 from .policy import MlpPolicy
 from .ptable import PolicyScore, PolicyTable
 from .render import TextRender
+from .rptable import ReachPolicyTable
 from .rstarts import ReachIndex
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
@@ -67,4 +70,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "PolicyTable", "PolicyScore", "build_ptable_library",
            "ReachResult", "SOLVE_FULL", "build_reach_library",
            "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library",
-           "ReachIndex", "build_rstarts_library"]
+           "ReachIndex", "build_rstarts_library",
+           "ReachPolicyTable", "build_rptable_library"]

@@ -7,7 +7,7 @@ An entry is the binding module itself, so nothing a binding knows is restated he
 iterate over this tuple.
 """
 from . import (_ac_cabi, _cabi, _loss_cabi, _optim_cabi, _policy_cabi, _ptable_cabi, _reach_cabi, _rexpert_cabi, _rollout_cabi,
-               _rstarts_cabi, _rtable_cabi, _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi)
+               _rptable_cabi, _rstarts_cabi, _rtable_cabi, _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi)
 
 LIBRARIES = (_cabi, _search_cabi, _table_cabi, _rollout_cabi, _policy_cabi, _train_cabi, _targets_cabi, _ac_cabi, _update_cabi,
              _loss_cabi, _optim_cabi, _starts_cabi)
@@ -25,7 +25,7 @@ ADDED = (_reach_cabi, _rtable_cabi, _rexpert_cabi)
 # checked by tests/test_libraries_since_cpu.py, which iterates over this tuple.  No test pins its length, and none may: a
 # library's own tests check that it is an entry, never how many there are - the next library is one more entry (DESIGN.md
 # section 23).
-SINCE = (_rstarts_cabi,)
+SINCE = (_rstarts_cabi, _rptable_cabi)
 
 
 def name(binding):

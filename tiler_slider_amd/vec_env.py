@@ -1316,7 +1316,7 @@ class VecTilerSliderEnv:
         return rollout_policy(self, steps, policy, select, epsilon, seed, step_index, board_offset, stats, log, advance)
 
     # ------------------------------------------------------------------ policy tables (lib/libtiler_slider_ptable.so)
-    def build_policy_table(self, policy, max_depth=252, max_bytes=4 << 30, logits=False):
+    def build_policy_table(self, policy, max_depth=252, max_bytes=4 << 30, logits=False, table=None):
         """A PolicyTable: the greedy play of `policy` (an MlpPolicy, or a PolicyNet / ActorCriticNet through its .policy()) from
         EVERY placement of every board's level, exactly, in two launches (include/tiler_slider_ptable.h: ts_ptable_actions, the
         network once per placement; ts_ptable_walk, the outcome of following its moves).  `.dist` uint8 [N, states] has
@@ -1325,14 +1325,30 @@ class VecTilerSliderEnv:
         lookup(), place_at_distance() and every other call that takes a DistanceTable take it as it is.  `.act` uint8 [N, states]
         is the move on each placement (255 on an invalid one) and, with logits=True, `.logits` float32 [N, states, 4] the values
         it was chosen from, bit-equal to policy_logits() on a board standing there.  Reads no tile and writes no state; no
-        sampling, no horizon, no start distribution.  max_bytes as build_table() (2 bytes per placement, 18 with the logits)."""
+        sampling, no horizon, no start distribution.  max_bytes as build_table() (2 bytes per placement, 18 with the logits).
+        table=rt, a ReachTable (build_reach_table()) of this environment's levels, one row per board: the same on the shapes
+        beyond the dense index space, over the states rt holds (include/tiler_slider_rptable.h: ts_rptable_actions,
+        ts_rptable_walk) - a ReachPolicyTable, a ReachTable itself: `.table` holds the policy's entries in rt's slots, `.act`
+        uint8 [N, slots] the move on each state's slot (255 on every other), `.logits` float32 [N, slots, 4]; lookup(),
+        build_reach_index() and through it place_at_distance() take it as they take rt.  9 bytes per slot, 25 with the logits."""
+        if table is not None:
+            from .rptable import build_policy_table
+            return build_policy_table(self, policy, table, max_depth, max_bytes, logits)
         from .ptable import build_policy_table
         return build_policy_table(self, policy, max_depth, max_bytes, logits)
 
-    def walk_actions(self, act, max_depth=252):
+    def walk_actions(self, act, max_depth=252, table=None, max_bytes=4 << 30):
         """build_policy_table()'s second launch alone, over a given action table: `act` uint8 [N, states] on the device, any bytes -
         a move 0 .. 3 is played, anything else stands still - gives the PolicyTable of that tabular policy.  Walking the
-        expert's moves reproduces build_table()."""
+        expert's moves reproduces build_table().  table=rt, a ReachTable of this environment's levels: `act` is uint8 [N, rt.slots],
+        read on the slots of rt's states, and the result the ReachPolicyTable of that tabular policy; walking the expert's moves
+        reproduces rt's entries.  The result takes 8 bytes a slot beside the byte of `act`: above `max_bytes` (9 bytes a slot,
+        as build_policy_table(table=rt) counts them) this raises; `max_bytes` is read on this path only.  A table of more than
+        8,192 slots (capacity above 4,096) is walked in its output row, every round reading the whole row
+        (include/tiler_slider_rptable.h: TS_RPTABLE_FORM_GLOBAL): long chains cost rounds x slots there."""
+        if table is not None:
+            from .rptable import walk_actions
+            return walk_actions(self, act, table, max_depth, max_bytes)
         from .ptable import walk_actions
         return walk_actions(self, act, max_depth)
 
@@ -1340,7 +1356,12 @@ class VecTilerSliderEnv:
         """PolicyScore of a PolicyTable against the optimal DistanceTable of the same levels (build_table()), one launch
         (ts_ptable_score), integers only and the same bits on every run: per level the valid, solvable, solved and optimally
         solved placements, those on which the policy's move is one of the expert's, the excess moves, and `solved_share`,
-        `optimal_share`, `agreement` over all levels as 0-dim device tensors."""
+        `optimal_share`, `agreement` over all levels as 0-dim device tensors.  A ReachPolicyTable is scored against the ReachTable
+        of the same levels and slots (ts_rptable_score): the same columns, counted over the states the table holds."""
+        from .rptable import ReachPolicyTable
+        if isinstance(ptable, ReachPolicyTable):
+            from .rptable import score_policy
+            return score_policy(self, ptable, table)
         from .ptable import score_policy
         return score_policy(self, ptable, table)
 
