@@ -14,10 +14,12 @@ lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_r
 lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy="reach") or trajectory_labels() of a ReachTable
 lib/libtiler_slider_rexpert.so, the first build_reach_index() or place_at_distance() of a ReachIndex
 lib/libtiler_slider_rstarts.so, the first build_policy_table(), walk_actions() or score_policy() of a ReachTable
-lib/libtiler_slider_rptable.so, and each fails loudly if its library is missing (no CPU fallback).
+lib/libtiler_slider_rptable.so, the first lookahead() or td_targets() lib/libtiler_slider_lookahead.so, and each fails loudly if its
+library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
+from ._lookahead_cabi import build_library as build_lookahead_library
 from ._loss_cabi import build_library as build_loss_library
 from ._optim_cabi import build_library as build_optim_library
 from ._policy_cabi import build_library as build_policy_library
@@ -42,6 +44,7 @@ from .actor_critic import ActorCriticNet
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
 from .gym_wrapper import GymVecTilerSlider
+from .lookahead import Lookahead
 from .loss import LossInfo, actor_critic_loss, actor_critic_loss_grads
 from .levels import ImageLoader, Level, pack_levels, parse_board_string
 from .moves import Move
@@ -71,4 +74,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "ReachResult", "SOLVE_FULL", "build_reach_library",
            "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library",
            "ReachIndex", "build_rstarts_library",
-           "ReachPolicyTable", "build_rptable_library"]
+           "ReachPolicyTable", "build_rptable_library",
+           "Lookahead", "build_lookahead_library"]

@@ -1388,6 +1388,36 @@ class VecTilerSliderEnv:
         from .actor_critic import trajectory_outputs
         return trajectory_outputs(self, net, rollout)
 
+    # ------------------------------------------------------------------ lookahead (lib/libtiler_slider_lookahead.so)
+    def lookahead(self, net, depth=2, rollout=None, leaf=None, gamma=1.0, reward=None):
+        """Lookahead(q, value, best, win_in): the values of `net` backed up through a full-width search of `depth` plies (1 .. 4) of
+        the exact environment, ONE launch (include/tiler_slider_lookahead.h: ts_lookahead) - on the boards as they stand
+        (q float32 [N, 4], value float32 [N], best uint8 [N], win_in uint8 [N]) or, with a Rollout that logged ("start", "pos"), on
+        every board it visited ([K, N, ...], row k the board step k was chosen on).
+          q[..., a] = r + gamma * (0 if the move wins, else the best backed-up value of the board after it), r = reward.step
+                      + reward.win on a winning move + reward.invalid on a move that changes nothing; at the last ply the value
+                      of a board is the leaf's
+          leaf: "value" - the value head of an ActorCriticNet (its default); "qmax" - the largest logit, the network read as a
+                Q-network (the default of a PolicyNet / MlpPolicy; an ActorCriticNet may ask for it); "zero" - no network is read
+                (the default of net=None): plain reward search
+          value = q.max(-1); best = the lowest action that attains it - step(best) plays the search's move, and as
+                trajectory_loss(labels=best) it is an expert-iteration target; win_in = the plies to the nearest win inside the
+                horizon, 0 if there is none
+        A board that is already won gets q = 0, value = 0, best = 255 (left alone by step(), no sample for a loss), win_in = 0.
+        An invalid move costs a ply like any other; there is no transposition table, no pruning and no timeout: reward.timeout,
+        reward.dist and reward.progress must be 0 (ValueError).  The results are targets and carry no grad_fn.  Shapes and widths
+        as rollout_policy(); checks and errors as trajectory_logits().  No state is touched."""
+        from .lookahead import lookahead
+        return lookahead(self, net, depth, rollout, leaf, gamma, reward)
+
+    def td_targets(self, net, rollout=None, gamma=0.99, reward=None):
+        """float32 [N, 4] or [K, N, 4]: the one-step targets of ALL FOUR actions of every board - lookahead(depth=1).q:
+        r(s, a) + gamma V(s') with an ActorCriticNet, r(s, a) + gamma max_a' Q(s', a') with a PolicyNet / MlpPolicy read as a
+        Q-network, 0 beyond a winning move and on a board that is already won.  One launch; no twin environment is stepped and
+        no successor board is encoded.  gather() the logged action's column for TD(0) or Q-learning."""
+        from .lookahead import lookahead
+        return lookahead(self, net, 1, rollout, None, gamma, reward).q
+
     # ------------------------------------------------------------------ trajectory targets (lib/libtiler_slider_targets.so)
     def trajectory_returns(self, rollout, gamma=0.99, lam=1.0, values=None, last_value=None, reward=None):
         """TrajectoryReturns(reward, adv, ret float32 [K, N], mask bool [K, N]) of a Rollout that logged its flags: per-step rewards,
