@@ -14,13 +14,14 @@ lib/libtiler_slider_ptable.so, the first solve_reachable() lib/libtiler_slider_r
 lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy="reach") or trajectory_labels() of a ReachTable
 lib/libtiler_slider_rexpert.so, the first build_reach_index() or place_at_distance() of a ReachIndex
 lib/libtiler_slider_rstarts.so, the first build_policy_table(), walk_actions() or score_policy() of a ReachTable
-lib/libtiler_slider_rptable.so, the first lookahead() or td_targets() lib/libtiler_slider_lookahead.so, and each fails loudly if its
-library is missing (no CPU fallback).
+lib/libtiler_slider_rptable.so, the first lookahead() or td_targets() lib/libtiler_slider_lookahead.so, the first
+rollout_policy(expert=...) lib/libtiler_slider_mixed.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
 from ._lookahead_cabi import build_library as build_lookahead_library
 from ._loss_cabi import build_library as build_loss_library
+from ._mixed_cabi import build_library as build_mixed_library
 from ._optim_cabi import build_library as build_optim_library
 from ._policy_cabi import build_library as build_policy_library
 from ._ptable_cabi import build_library as build_ptable_library
@@ -75,4 +76,4 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library",
            "ReachIndex", "build_rstarts_library",
            "ReachPolicyTable", "build_rptable_library",
-           "Lookahead", "build_lookahead_library"]
+           "Lookahead", "build_lookahead_library", "build_mixed_library"]

@@ -198,15 +198,22 @@ class Rollout:
     device tensors, None where not asked for.  wins, finished, first_win, win_moves, reward_sum int32 [N]; flags uint8 [N] (the
     last step's); act_log, flags_log uint8 [steps, N]; pos_log cell ids [steps, T, N] (the compact form ts_encode re-encodes).
     rollout_policy() can also log logits_log float32 [steps, N, 4] (include/tiler_slider_policy.h) and start_pos, cell ids [T, N]:
-    a copy of the cells taken before the launch (log "start"; with pos_log it is what trajectory_logits() reads)."""
+    a copy of the cells taken before the launch (log "start"; with pos_log it is what trajectory_logits() reads).
+    rollout_policy(expert=...) can also log what the expert's table answers on the board each step was chosen on
+    (include/tiler_slider_mixed.h): expert_log uint8 [steps, N] its move (255: none), moves_log int16 [steps, N], best_log uint8
+    [steps, N] - trajectory_labels()' action, moves and best - and who_log uint8 [steps, N]: 0 the network played, 1 the expert,
+    2 the random draw."""
 
     FIELDS = ("wins", "finished", "first_win", "win_moves", "reward_sum", "flags", "act_log", "flags_log", "pos_log")
-    __slots__ = FIELDS + ("steps", "logits_log", "start_pos")
+    MIXED_LOGS = ("expert_log", "moves_log", "best_log", "who_log")
+    __slots__ = FIELDS + ("steps", "logits_log", "start_pos") + MIXED_LOGS
 
     def __init__(self, steps, **tensors):
         self.steps = int(steps)
         self.logits_log = tensors.get("logits_log")
         self.start_pos = tensors.get("start_pos")
+        for name in self.MIXED_LOGS:
+            setattr(self, name, tensors.get(name))
         for name in self.FIELDS:
             setattr(self, name, tensors.get(name))
 
@@ -1303,7 +1310,7 @@ class VecTilerSliderEnv:
         return policy_logits(self, policy)
 
     def rollout_policy(self, steps, policy, select="sample", epsilon=0.0, seed=0, step_index=0, board_offset=0, stats=True, log=(),
-                       advance=True):
+                       advance=True, expert=None, beta=0.0, rows=None):
         """rollout() with a network choosing every action, still ONE launch (include/tiler_slider_policy.h: ts_policy_rollout):
         at every step the kernel evaluates `policy` (an MlpPolicy) on the board as it stands and plays
           select "greedy": the lowest action among the largest logits
@@ -1311,7 +1318,21 @@ class VecTilerSliderEnv:
         replaced by that stream's random action with probability `epsilon`.  seed, step_index, board_offset, stats, log and
         advance are rollout()'s; `log` also accepts "logits": Rollout.logits_log float32 [steps, N, 4], the values each action was
         chosen from, and "start": Rollout.start_pos, a copy of the cells before the launch (what trajectory_logits() needs beside
-        "pos").  Shapes as rollout("random"), hidden widths 1 .. 64: ValueError otherwise."""
+        "pos").  Shapes as rollout("random"), hidden widths 1 .. 64: ValueError otherwise.
+        expert=table (anything lookup() takes: a DistanceTable or PolicyTable, a ReachTable or ReachPolicyTable; `rows` as in
+        lookup()): the table's expert SHARES the play, still one launch (include/tiler_slider_mixed.h: ts_mixed_rollout).  Per
+        board and step the expert's move is played with probability `beta` - DAgger's behaviour policy - wherever it has one
+        (elsewhere the network plays), and the random action still replaces either with probability `epsilon`.  The kernel looks
+        the table up on every board it visits, so `log` also accepts "expert", "moves", "best" - Rollout.expert_log, moves_log,
+        best_log: byte for byte trajectory_labels()' action, moves and best of this rollout, without the second launch - and
+        "who": Rollout.who_log, 0 where the network played, 1 the expert, 2 the random draw.  With beta = 0 and none of the three
+        asked for, the table is not read and the play is rollout_policy()'s without an expert.  Without `expert`, beta != 0, rows
+        and the four logs are a ValueError."""
+        if expert is not None:
+            from .mixed import rollout_mixed
+            return rollout_mixed(self, steps, policy, expert, beta, rows, select, epsilon, seed, step_index, board_offset, stats, log, advance)
+        if beta != 0 or rows is not None:
+            raise ValueError("beta and rows belong to expert=: without an expert the network plays alone")
         from .policy import rollout_policy
         return rollout_policy(self, steps, policy, select, epsilon, seed, step_index, board_offset, stats, log, advance)
 
