@@ -15,7 +15,7 @@ lookup() of a ReachTable lib/libtiler_slider_rtable.so, the first rollout(policy
 lib/libtiler_slider_rexpert.so, the first build_reach_index() or place_at_distance() of a ReachIndex
 lib/libtiler_slider_rstarts.so, the first build_policy_table(), walk_actions() or score_policy() of a ReachTable
 lib/libtiler_slider_rptable.so, the first lookahead() or td_targets() lib/libtiler_slider_lookahead.so, the first
-rollout_policy(expert=...) lib/libtiler_slider_mixed.so, and each fails loudly if its library is missing (no CPU fallback).
+rollout_policy(expert=...) lib/libtiler_slider_mixed.so, the first trajectory_vtrace() lib/libtiler_slider_vtrace.so, and each fails loudly if its library is missing (no CPU fallback).
 """
 from ._ac_cabi import build_library as build_ac_library
 from ._cabi import TilerSliderLibraryError, build_library
@@ -41,6 +41,7 @@ from ._table_cabi import build_library as build_table_library
 from ._targets_cabi import build_library as build_targets_library
 from ._train_cabi import build_library as build_train_library
 from ._update_cabi import build_library as build_update_library
+from ._vtrace_cabi import build_library as build_vtrace_library
 from .actor_critic import ActorCriticNet
 from .env import GameState, TilerSliderEnv
 from .factory import TilerSliderEnvFactory, simple_level
@@ -58,6 +59,7 @@ from .rptable import ReachPolicyTable
 from .rstarts import ReachIndex
 from .targets import RewardWeights, TrajectoryReturns
 from .train import PolicyNet
+from .vtrace import VtraceTargets
 from .vec_env import DistanceTable, ReachResult, ReachTable, Rollout, StartInfo, StepInfo, VecTilerSliderEnv
 
 __version__ = "0.1.0"
@@ -76,4 +78,5 @@ __all__ = ["GameState", "Move", "TilerSliderEnv", "TilerSliderEnvFactory", "Imag
            "ReachTable", "SOLVE_ABSENT", "build_rtable_library", "build_rexpert_library",
            "ReachIndex", "build_rstarts_library",
            "ReachPolicyTable", "build_rptable_library",
-           "Lookahead", "build_lookahead_library", "build_mixed_library"]
+           "Lookahead", "build_lookahead_library", "build_mixed_library",
+           "VtraceTargets", "build_vtrace_library"]

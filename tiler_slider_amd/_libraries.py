@@ -7,7 +7,8 @@ An entry is the binding module itself, so nothing a binding knows is restated he
 iterate over this tuple.
 """
 from . import (_ac_cabi, _cabi, _lookahead_cabi, _loss_cabi, _mixed_cabi, _optim_cabi, _policy_cabi, _ptable_cabi, _reach_cabi, _rexpert_cabi, _rollout_cabi,
-               _rptable_cabi, _rstarts_cabi, _rtable_cabi, _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi)
+               _rptable_cabi, _rstarts_cabi, _rtable_cabi, _search_cabi, _starts_cabi, _table_cabi, _targets_cabi, _train_cabi, _update_cabi,
+               _vtrace_cabi)
 
 LIBRARIES = (_cabi, _search_cabi, _table_cabi, _rollout_cabi, _policy_cabi, _train_cabi, _targets_cabi, _ac_cabi, _update_cabi,
              _loss_cabi, _optim_cabi, _starts_cabi)
@@ -26,7 +27,7 @@ ADDED = (_reach_cabi, _rtable_cabi, _rexpert_cabi)
 # library's own tests check that it is an entry, never how many there are - the next library is one more entry (DESIGN.md
 # section 23).  tests/test_rptable_cpu.py does assert that the reach policy tables are the LAST entry, so a new library goes in
 # front of _rptable_cabi: the order inside this tuple is the order of build() and nothing else.
-SINCE = (_rstarts_cabi, _lookahead_cabi, _mixed_cabi, _rptable_cabi)
+SINCE = (_rstarts_cabi, _lookahead_cabi, _mixed_cabi, _vtrace_cabi, _rptable_cabi)
 
 
 def name(binding):

@@ -1458,6 +1458,25 @@ class VecTilerSliderEnv:
         from .targets import trajectory_returns
         return trajectory_returns(self, rollout, gamma, lam, values, last_value, reward)
 
+    def trajectory_vtrace(self, rollout, logits=None, values=None, last_value=None, gamma=0.99, lam=1.0, rho_bar=1.0, c_bar=1.0,
+                          select="sample", epsilon=0.0, beta=0.0, reward=None):
+        """VtraceTargets(reward, adv, ret, mask, weight, log_mu) of a Rollout whose actions were NOT drawn from the network being
+        trained - rollout_policy(expert=, beta=), epsilon > 0, select "greedy", or a log replayed after the weights have moved -
+        in ONE launch (include/tiler_slider_vtrace.h: ts_traj_vtrace).  V-trace (Espeholt et al. 2018): trajectory_returns()'
+        backward recursion with the truncated importance weights rho = min(rho_bar, pi / mu) and c = lam min(c_bar, pi / mu)
+        inside; `ret` is the V-trace target v_s, `adv` the policy-gradient advantage rho (r + gamma v_(s+1) - V) with its weight
+        included, `weight` pi / mu unclipped and `log_mu` the log of the behaviour probability of the action played.  mu follows
+        exactly from what the rollout logged - it needs log ("flags", "act", "logits"), and ("expert",) where beta > 0 - and from
+        the `select`, `epsilon` and `beta` it was made with, which the caller passes again.
+          logits: float32 [K, N, 4], the network's logits NOW (trajectory_logits() / trajectory_outputs(); detached).  None: the
+                  logged logits - with select "sample" and epsilon = beta = 0 every weight is then exactly 1 and, for bars >= 1,
+                  `ret` is trajectory_returns()' and `adv` its adv at lam = 1
+          values, last_value, gamma, reward: trajectory_returns()'; masks, void steps and episode ends as there
+        vt.returns is a TrajectoryReturns: trajectory_loss(logits, rollout, vt.returns, values=v) at clip=0 is the V-trace
+        actor-critic loss.  Shapes as rollout("random"): ValueError otherwise.  No state is touched."""
+        from .vtrace import trajectory_vtrace
+        return trajectory_vtrace(self, rollout, logits, values, last_value, gamma, lam, rho_bar, c_bar, select, epsilon, beta, reward)
+
     def trajectory_labels(self, rollout, table, rows=None):
         """(moves int16 [K, N], best uint8 [K, N], action uint8 [K, N]): lookup_bits() and expert_actions_from() of `table` on every
         board a Rollout visited - row k is the answer on the board step k was chosen on (start_pos, then pos_log[k - 1]) - in ONE
